@@ -23,6 +23,13 @@ gathered back to rank 0 (the only exchange steps of the path).  Weak scaling.
 Named workloads (--workload): config2 = the default above; config3 = TTS-1 32 utterances
 per GPU; config4 = TTS-1-Max 8 utterances per GPU (BASELINE configs[3]: bs=64 over 8 GPUs).
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line.  `--full`
+adds everything that takes runs of its own after the timed region: the codec leg alone, the
+per-kernel roofline, the bs=32 / streaming / encoder secondaries, the TTS-1-Max line of a
+distributed run and the CPU baseline (`--no-secondary`, `--no-max-line` and
+`--no-cpu-baseline` take single legs out of it again).  `--dump-outputs DIR` writes what the
+last timed step returned to its caller (generated ids and waveforms) as .npy files.
+
 Prints ONE JSON line (rank 0).
 """
 
@@ -65,6 +72,11 @@ def main():
     ap.add_argument("--prompt-codes", type=int, default=150)
     ap.add_argument("--text-tokens", type=int, default=39)
     ap.add_argument("--new", type=int, default=500)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the codec leg alone, the per-kernel roofline, the "
+                         "secondary lines and the CPU baseline (a plain run times the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (generated ids, waveforms) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=96)
     ap.add_argument("--kernel-iters", type=int, default=30)
@@ -131,7 +143,7 @@ def main():
 
     max_seq = P + N + 16
     t0 = time.time()
-    secondary = (world == 1 and not args.no_secondary and args.arch == "tts1" and B == 1)
+    secondary = (args.full and world == 1 and not args.no_secondary and args.arch == "tts1" and B == 1)
     lm = MI355XSpeechLM.synthetic(arch, seed=0x5EED, device=local, max_batch=max(B, 32 if secondary else 1),
                                   max_seq_len=max_seq)
     dec = MI355XAudioDecoder.synthetic(carch, seed=0xC0DEC, device=local, max_codes=args.prompt_codes + N + 8)
@@ -142,12 +154,12 @@ def main():
         if dist is not None and local_prompts is None:
             # rank 0's request batch broadcast over RCCL, each rank generates +
             # voices its contiguous shard, codes AND waveforms gathered to rank 0 (dp.py)
-            _, wavs, (n, _) = dp.synthesize_sharded(
+            ids, wavs, (n, _) = dp.synthesize_sharded(
                 prompts_all if rank == 0 else None, lm, dec, dev, max_new=N,
                 prompt_codes=lambda p: synthetic_codes(lm, p[-args.prompt_codes:]),
                 to_codes=lambda ids: synthetic_codes(lm, ids), balance="contiguous", min_new_tokens=N,
                 eos_token_id=vocab.speech_end_id, repetition_penalty=1.1, wav_out=wav_buf)
-            return n, wavs  # (rank 0: waveforms as host tensors, as AudioDecoder.decode returns them)
+            return n, wavs, ids  # (rank 0: waveforms as host tensors, as AudioDecoder.decode returns them)
         prompts = local_prompts if local_prompts is not None else prompts_all[rank * B:(rank + 1) * B]
         new = lm.generate_batch(prompts, max_length=P + N, min_new_tokens=N, eos_token_id=vocab.speech_end_id,
                                 repetition_penalty=1.1)
@@ -158,7 +170,7 @@ def main():
         # waveforms to host memory inside the timed region: the reference's boundary
         # (decoding.py:84-89 returns `.detach().cpu()`), ~1.25 MB per 10-s utterance
         wav = dec.decode_batch(utts)
-        return sum(len(n) for n in new), wav
+        return sum(len(n) for n in new), wav, new
 
     wav_buf = torch.empty(max(B, 32 if secondary else 1) * codes_per_utt * carch.samples_per_code,
                           dtype=torch.float32, device=dev)
@@ -172,8 +184,9 @@ def main():
     n_codes = 0
     lm_prefill = lm_decode = 0.0
     dec_steps = 0
+    last = None
     for _ in range(args.steps):
-        n, _ = one_step()
+        n, *last = one_step()
         n_codes += n
         a, b, k = lm.last_timing()
         lm_prefill += a
@@ -196,6 +209,46 @@ def main():
     audio_s = N / carch.token_rate  # seconds of audio per utterance
     rtf = (elapsed / args.steps) / audio_s  # wall per utterance-batch / audio seconds (per GPU)
 
+    if rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, ids=last[1], wavs=last[0])
+
+    # ---- the headline line: what the timed steps alone give
+    line = {
+        "metric": "audio-codes/sec + RTF@24kHz, TTS-1 bs=1/32, at 1/2/4/8 MI355X",
+        "value": round(codes_per_s, 2),
+        "unit": "audio-codes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": f"synthetic (random-init {arch.name} weights, synthetic prompt ids of the reference prompt shape)",
+        "rtf": round(rtf, 5),
+        "x_realtime": round(1.0 / rtf * B, 2),
+        "lm_prefill_ms": round(lm_prefill / args.steps, 3),
+        "lm_decode_ms": round(lm_decode / args.steps, 3),
+        "prefill_roofline": prefill_roofline(arch, [len(q) for q in prompts_all[rank * B:(rank + 1) * B]],
+                                             lm_prefill / args.steps),
+        "config": {
+            "workload": f"{arch.name} bf16 bs={B}/GPU: prompt {P} tokens ({args.prompt_codes} codes), "
+                        f"{N} greedy codes, codec {carch.name} on {codes_per_utt} codes",
+            "model": MODEL_NAMES.get(arch.name, arch.name) + f" + xcodec2-style codec {carch.name}",
+            "global_batch": B * world,
+            "seq_len": P + N,
+            "parallelism": f"dp{world}",
+        },
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below takes runs of its own after the timed region
     # ---- the codec leg alone (B utterances of prompt + N codes, one ragged pass), after the timed region
     rngc = np.random.default_rng(7)
     uttsc = [rngc.integers(0, 65536, size=codes_per_utt).tolist() for _ in range(B)]
@@ -374,43 +427,46 @@ def main():
         cpu = cpu_baseline(arch, carch, prompts_all[0], N, args)
 
     if rank == 0:
-        line = {
-            "metric": "audio-codes/sec + RTF@24kHz, TTS-1 bs=1/32, at 1/2/4/8 MI355X",
-            "value": round(codes_per_s, 2),
-            "unit": "audio-codes/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16",
-            "data": f"synthetic (random-init {arch.name} weights, synthetic prompt ids of the reference prompt shape)",
-            "rtf": round(rtf, 5),
-            "x_realtime": round(1.0 / rtf * B, 2),
-            "lm_prefill_ms": round(lm_prefill / args.steps, 3),
-            "lm_decode_ms": round(lm_decode / args.steps, 3),
+        line.update({
             "codec_ms": round(codec_ms, 3),
             "codec_to_host_ms": round(codec_host_ms, 3),
             "codec_roofline": codec_roofline(carch, codes_per_utt, B, codec_ms),
-            "prefill_roofline": prefill_roofline(arch, [len(q) for q in prompts_all[rank * B:(rank + 1) * B]],
-                                                 lm_prefill / args.steps),
-            "config": {
-                "workload": f"{arch.name} bf16 bs={B}/GPU: prompt {P} tokens ({args.prompt_codes} codes), "
-                            f"{N} greedy codes, codec {carch.name} on {codes_per_utt} codes",
-                "model": MODEL_NAMES.get(arch.name, arch.name) + f" + xcodec2-style codec {carch.name}",
-                "global_batch": B * world,
-                "seq_len": P + N,
-                "parallelism": f"dp{world}",
-            },
             "roofline": roofline,
             "cpu_baseline": cpu,
             "secondary": sec,
-        }
+        })
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20  # everything --dump-outputs writes stays under this
+
+
+def dump_outputs(out_dir, ids, wavs, max_bytes=DUMP_MAX_BYTES):
+    """What one step returned to its caller, as DIR/<name>.npy: `ids` [utterances, longest]
+    float64, the generated ids of each utterance padded with -1; `waveform_lengths`
+    [utterances] float64; `waveforms` float32, the utterances' samples end to end.  Past
+    half the size limit the waveforms are a fixed sample instead: `waveform_sample_index`
+    (float64, sorted positions in the end-to-end array, drawn with seed 0) and their values."""
+    os.makedirs(out_dir, exist_ok=True)
+    longest = max((len(u) for u in ids), default=0)
+    idm = np.full((len(ids), longest), -1.0, dtype=np.float64)
+    for r, u in enumerate(ids):
+        idm[r, :len(u)] = u
+    flat = np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs])
+    lens = np.array([np.asarray(w).size for w in wavs], dtype=np.float64)
+    assert idm.nbytes + lens.nbytes < max_bytes // 4, "ids alone outgrow the dump's size limit"
+    np.save(os.path.join(out_dir, "ids.npy"), idm)
+    np.save(os.path.join(out_dir, "waveform_lengths.npy"), lens)
+    if flat.nbytes > max_bytes // 2:
+        keep = max_bytes // 2 // 12  # 8 bytes of index + 4 of value per kept sample
+        idx = np.sort(np.random.default_rng(0).choice(flat.size, size=keep, replace=False))
+        np.save(os.path.join(out_dir, "waveform_sample_index.npy"), idx.astype(np.float64))
+        flat = flat[idx]
+    elif os.path.exists(os.path.join(out_dir, "waveform_sample_index.npy")):
+        os.remove(os.path.join(out_dir, "waveform_sample_index.npy"))  # (an earlier, larger run's)
+    np.save(os.path.join(out_dir, "waveforms.npy"), flat)
 
 
 def tts1max_sharded(args, dist, dev, rank, world, per_gpu=8):
