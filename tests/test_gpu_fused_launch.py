@@ -142,12 +142,10 @@ def test_batched_fused_qkv_attention_equals_separate_launches(arch, rows, L, n_l
     assert outs["fused"] == outs["no_oproj"] == outs["separate"], outs
 
 
-@pytest.mark.parametrize("env", [{"TTS_FATTN_FIRST": "1"}, {"TTS_FATTN_FIRST": "1", "TTS_FUSED_OPROJ": "0"},
-                                 {"TTS_FUSED_OPROJ": "0"}, {"TTS_FUSED_ATTN": "0"}])
+@pytest.mark.parametrize("env", [{"TTS_FUSED_OPROJ": "0"}, {"TTS_FUSED_ATTN": "0"}])
 def test_one_row_grid_orders_equal(env):
-    """The one-row fused launch in round 3's grid order (TTS_FATTN_FIRST=1: attention
-    workgroups first, o_proj on the projection workgroups after their QKV unit), with and
-    without o_proj fused, gives the default launch's bits (and the separate launches')."""
+    """The one-row fused launch without o_proj fused, and the separate launches, give the
+    default launch's bits."""
     outs = []
     for e in ({}, env):
         r = subprocess.run([sys.executable, "-c", _ROWS_CHILD, ROOT, "tts1", "1", "1100", "24"],

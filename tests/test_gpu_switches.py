@@ -54,11 +54,8 @@ CASES = [
     ("TTS_FUSED_OPROJ=0", "tts1", "1,8"),
     ("TTS_FUSED_OPROJ_ROWS=0", "tts1", "8"),
     ("TTS_FATTN_ROWS=0", "tts1", "8"),
-    ("TTS_FATTN_FIRST=1", "tts1", "1,8"),
     ("TTS_CSPLIT=0", "tts1", "1,8"),
     ("TTS_QKV_DEFER=0", "tts1", "24"),
-    ("TTS_RING4=0", "tts1", "8,24"),
-    ("TTS_RING4_32=0", "tts1", "24"),
     ("TTS_COMBINE_FIXED=0", "tts1", "24"),
     ("TTS_SLICED_GRID=0", "tts1", "24"),
     ("TTS_HEAD_GRID=512", "tts1", "1,24"),

@@ -90,8 +90,7 @@ struct LmWork {
   DevBuf blocks;                                    // prefill query blocks (int4, lm_attn.hip)
   int nblocks = 0;
   DevBuf gran, ferr;                                // fused QKV+attention: granules [QKV/2] u64, error flag
-  DevBuf xgran;                                     // norm-once hand-off: hidden-row granules [2][B][hidden/2] u64
-  DevBuf epoch;                                     // decode-step counter (u32; the hand-off's tags)
+  DevBuf epoch;                                     // decode-step counter (u32; the screened head's step keys)
   DevBuf lpart_v, lpart_i;                          // lm_head argmax partials
   DevBuf hub, hlb;                                  // screened head: check-mode score bounds [B][V], per-row max lower bound (u64)
   DevBuf hxq, hxs;                                  // screened head at 17..32 rows: the rows quantised [2B][hidden] i8, their stats

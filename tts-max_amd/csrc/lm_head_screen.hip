@@ -43,10 +43,7 @@ namespace {
 
 constexpr int kScrWaves = 4;  // screen workgroup: 4 waves, one per SIMD
 constexpr int kScrKU = 8;     // 1-KiB int8 blocks (64 k each) per stage
-#ifndef TTS_SCR_R
-#define TTS_SCR_R 2
-#endif
-constexpr int kScrR = TTS_SCR_R;  // stages in flight per wave (experiment builds: -DTTS_SCR_R=4)
+constexpr int kScrR = 2;      // stages in flight per wave
 
 // the float nearest a double, rounded up (bounds stay bounds)
 TTS_DEV float f_up(double d) {
@@ -220,10 +217,6 @@ TTS_DEV void quant_row(const u32x4_t (&v)[CPL], int lane, int8_t* hi_row, int8_t
 // continues wave w - 1's accumulator through LDS), the same epilogue — and the workgroup writes
 // its argmax partial (lowest index on ties) for finalize_greedy_kernel.
 constexpr int kScrMaxUPW = 16;  // units a wave streams (host-checked: units <= 16 * ur)
-#ifndef TTS_SCR_DB32
-#define TTS_SCR_DB32 0
-#endif
-constexpr bool kScrDB32 = TTS_SCR_DB32;  // two flagged units in flight at K 4096 too (AGPRs hold the second): measured slower (165 -> 167 us at TTS-1-Max 8 rows), off
 #ifdef TTS_SCR_PROBE
 constexpr int kScrProbe = TTS_SCR_PROBE;  // timing probes only (scripts: wrong ids): 1 no MFMA, 2 no epilogue
 #else
@@ -352,7 +345,7 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
     // (the A fragments are the same for every unit: one m-tile at K 2048 keeps them in registers
     // across units, 128 VGPRs; larger images are re-read from LDS per unit, not hoisted)
     int aoff = 0;
-    if constexpr (MT * KT8 > 32 || kScrR > 2) asm volatile("" : "+v"(aoff));
+    if constexpr (MT * KT8 > 32) asm volatile("" : "+v"(aoff));
     // this unit's epilogue operands, issued behind its first stages and ahead of their refills
     const int c = u * 16 + col;
     const float4 cs = a.cst[c];
@@ -570,7 +563,7 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
         }
     }
   };
-  if constexpr (!PRE && (KTW <= 16 || kScrDB32)) {
+  if constexpr (!PRE && KTW <= 16) {
     // two units in flight: the next flagged unit's tiles load while this one's chain runs (the
     // loads are unconditional — an index past the list repeats the last unit, never used — so
     // the chain's waits count only its own loads)

@@ -94,7 +94,7 @@ struct StepState {
   int* n_active;      // [1]
   uint16_t* counts;   // [B][V] new-token counts (frequency penalty) or nullptr
   unsigned long long* row_seed;  // [B] sampling key of each row
-  uint32_t* epoch;    // [1] step counter (+1 by the finalize of every step: the norm-once hand-off's tags)
+  uint32_t* epoch;    // [1] step counter (+1 by the finalize of every step: the screened head's keys)
   int eos_id;
   int min_new;
 };
@@ -143,41 +143,22 @@ struct WgemmArgs {
   AttnArgs fa;                // the attention of this layer (its output row: fa.out)
   int fattn_wgs = 0;          // attention workgroups appended to the grid (0: not fused)
   int fattn_layer = 0;
-  // grid order.  0 (default): the projection workgroups, then the attention workgroups, then
-  // (fo_units > 0) one o_proj workgroup per o_proj unit: every workgroup waits only on blocks
-  // of lower index, and blocks are dispatched in index order, so the launch completes whatever
-  // else occupies the GPU (no co-residency needed).  1 (round-3 order, TTS_FATTN_FIRST=1): the
-  // attention workgroups first and o_proj on the projection workgroups after their QKV unit —
-  // circular waits, so it needs the whole grid resident (grid <= CUs, checked at launch).
-  int fattn_first = 0;
+  // grid order: the projection workgroups, then the attention workgroups, then (fo_units > 0)
+  // one o_proj workgroup per o_proj unit: every workgroup waits only on blocks of lower index,
+  // and blocks are dispatched in index order, so the launch completes whatever else occupies
+  // the GPU (no co-residency needed)
   int* fattn_err = nullptr;   // set to 1 if a granule wait timed out; later waits then give up at once
   int fattn_spins = 1 << 16;  // polls (s_sleep 1 each, ~0.1 s in all) before a wait gives up
   // o_proj fused behind the attention (fo_units > 0): the attention workgroups also publish
   // the bf16 attention row as granules (gran + N/2, same tag); o_proj unit b (tiled weights
-  // fo_w, layout rounds fo_ur, one round) runs on the grid's b-th o_proj workgroup (order 0)
-  // or on projection workgroup b after its QKV unit (order 1), with the residual epilogue on
-  // fo_resid (the hidden row), its o_proj weights loaded while the attention runs
-  // (2..16 rows, order 0: the attention rows' granules at gran + M*N/2, row m's H*D/2 at
-  // m*H*D/2; o_proj's layout K chunks fo_kc; fo_resid holds the M hidden rows)
+  // fo_w, layout rounds fo_ur, one round) runs on the grid's b-th o_proj workgroup, with the
+  // residual epilogue on fo_resid (the hidden row), its o_proj weights loaded while the
+  // attention runs
+  // (2..16 rows: the attention rows' granules at gran + M*N/2, row m's H*D/2 at m*H*D/2;
+  // o_proj's layout K chunks fo_kc; fo_resid holds the M hidden rows)
   const bf16_t* fo_w = nullptr;
   int fo_units = 0, fo_ur = 0, fo_kc = 1;
   bf16_t* fo_resid = nullptr;
-  // RMSNorm once per row, by the producer launch (2..32 decode rows; round 6): the launch's
-  // residual epilogue (fused o_proj of the QKV launch, or the down projection's own) also
-  // publishes every pair of the updated hidden row as a granule {bf16 pair, tag = (step << 6) |
-  // layer} in nw_gran [M][hid / 2], and nrm_wgs = M workgroups appended last in the grid (each
-  // waits only on lower blocks) gather one row each and write RMSNorm(row, nw_w) to nw_out
-  // [M][hid] in the canonical order (chunk_sumsq per 16 B, the wave DPP tree per 512 values,
-  // segments in order): the same bits as every other RMSNorm path.  The consumer launch then
-  // stages normalised rows instead of every workgroup normalising every row.  The step counter
-  // (*nw_epoch, one scalar load: no registers held through the weight stream) advances at every
-  // decode step, so two launches that write one granule region never share a tag.
-  int nrm_wgs = 0;
-  const bf16_t* nw_w = nullptr;
-  bf16_t* nw_out = nullptr;
-  uint64_t* nw_gran = nullptr;
-  const uint32_t* nw_epoch = nullptr;
-  int nw_layer = 0, nw_hid = 0;
   unsigned long long* stamps = nullptr;  // diagnostic build only (TTS_STAMPS): [block][8]
   int csplit = 1;     // 2: each 16-column unit runs as two 8-column halves (twice the workgroups; filled in by launch_wgemm)
   int diag = 0;       // timing diagnostics only (TTS_WGEMM_DIAG): 1 no prologue, 2 no epilogue, 8 barrier before the stream, 64 per-wave norm-end stamps

@@ -125,7 +125,7 @@ __global__ void finalize_greedy_kernel(const float* __restrict__ pv, const int* 
                                        int hidden) {
   __shared__ int lds[16];
   const int b = blockIdx.x;
-  // the step counter (norm-once hand-off tags, WgemmArgs::nw_epoch): +1 per step, every step
+  // the step counter (the screened head's keys, HeadScreenArgs::epoch): +1 per step, every step
   if (b == 0 && threadIdx.x == 0 && st.epoch) __hip_atomic_fetch_add(st.epoch, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   finalize_row<256, false>(pv + (size_t)b * part_stride, pi + (size_t)b * part_stride, nparts, st, b, embed, x,
                            hidden, lds);
