@@ -79,7 +79,7 @@ template <int D>
 __global__ __launch_bounds__(dec_nw<D>() * 64) void attn_decode_kernel(AttnArgs a) {
   constexpr int PW = dec_pw<D>(), NW = dec_nw<D>();
   using C = DecShape<D, PW>;
-  __shared__ __attribute__((aligned(16))) float qs[DEC_G * D];
+  __shared__ __attribute__((aligned(16))) bf16_t qs[DEC_G * D];
   __shared__ __attribute__((aligned(16))) bf16_t knew[D];
   __shared__ __attribute__((aligned(16))) bf16_t vnew[D];
   __shared__ __attribute__((aligned(16))) float red[dec_red_floats<D, NW>()];
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(dec_nw<D>() * 64) void attn_decode_kernel(AttnArgs 
   for (int i = tid; i < DEC_G * D + D; i += NW * 64) {
     if (i < DEC_G * D) {
       const int g = i / D, d = i % D;
-      qs[i] = rope_at<D>(qsrc + g * D, d, cosr, sinr);
+      qs[i] = f2bf(rope_at<D>(qsrc + g * D, d, cosr, sinr));
     } else {
       const int d = i - DEC_G * D;
       knew[d] = f2bf(rope_at<D>(ksrc, d, cosr, sinr));

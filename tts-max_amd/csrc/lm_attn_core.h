@@ -66,7 +66,8 @@ TTS_DEV int dec_pos(int base, int mt, int row) {
 // loads: a fixed load count keeps the compiler's vmcnt waits exact.  O32: 32-bit element
 // offsets inside the (slot, kv head) block (S * D < 2^31) — in the standalone kernel the 64-bit
 // ones stayed live across the passes in register pairs and spilled; the fused consumer
-// allocates best with the 64-bit form.  (Addresses only: the same bits either way.)
+// allocates best with the 64-bit form at head dim 64 and with the 32-bit one at 128.
+// (Addresses only: the same bits either way.)
 template <int D, int PW, bool O32 = false>
 TTS_DEV void dec_load_k(const bf16_t* kc, int base, int ctx, int lane,
                         u32x4_t (&kf)[DecShape<D, PW>::MT][DecShape<D, PW>::KS]) {
@@ -103,21 +104,31 @@ TTS_DEV void dec_load_v(const bf16_t* vtc, int S, int base, int lane,
 // are read unconditionally and merged with bit masks (a select whose operand is a load is
 // otherwise turned into a branch around the load, and every such branch also drains vmcnt).
 TTS_DEV uint32_t bits_sel(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }
+// Only the wave whose positions [base, base + PW) reach the new position pn = ctx - 1 has
+// anything to patch or to mask: below pn dec_patch_k's mask is 0, dec_patch_v's keep is all
+// ones and its put 0, and every position is < ctx.  One wave per pass is such a tail wave (the
+// waves past ctx do not run), so the others skip the patches and the < ctx select — the same
+// bits.  The branches are register-critical (the kernels sit at 116..128 VGPRs): the condition
+// goes through readfirstlane, each branch stands between scheduling barriers, the V patch comes
+// after the scores (kf is dead by then; both patches in one branch spilled 14..30 VGPRs at
+// head dim 128), and dec_patch_k reads the new k one k-step at a time (all at once: 4 spills).
+template <int PW>
+TTS_DEV bool dec_tail(int base, int ctx) { return __builtin_amdgcn_readfirstlane(base + PW > ctx - 1) != 0; }
 template <int D, int PW>
 TTS_DEV void dec_patch_k(int base, int ctx, int lane, const bf16_t* knew,
                          u32x4_t (&kf)[DecShape<D, PW>::MT][DecShape<D, PW>::KS]) {
   using C = DecShape<D, PW>;
   const int c = lane & 15, g = lane >> 4, pn = ctx - 1;
-  u32x4_t kn[C::KS];
+  uint32_t m[C::MT];
 #pragma unroll
-  for (int ks = 0; ks < C::KS; ++ks) kn[ks] = *(const u32x4_t*)(knew + 32 * ks + 8 * g);
+  for (int mt = 0; mt < C::MT; ++mt) m[mt] = dec_pos(base, mt, c) == pn ? 0xffffffffu : 0u;
 #pragma unroll
-  for (int mt = 0; mt < C::MT; ++mt) {
-    const uint32_t m = dec_pos(base, mt, c) == pn ? 0xffffffffu : 0u;
+  for (int ks = 0; ks < C::KS; ++ks) {
+    const u32x4_t kn = *(const u32x4_t*)(knew + 32 * ks + 8 * g);
 #pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks)
+    for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) kf[mt][ks][q] = bits_sel(m, kn[ks][q], kf[mt][ks][q]);
+      for (int q = 0; q < 4; ++q) kf[mt][ks][q] = bits_sel(m[mt], kn[q], kf[mt][ks][q]);
   }
 }
 template <int D, int PW>
@@ -148,21 +159,19 @@ TTS_DEV void dec_patch_v(int base, int ctx, int lane, const bf16_t* vnew,
   }
 }
 
-// q B fragment of k-step ks (roped q of the group's four heads, fp32 LDS holding bf16
-// values; read at each use: registers are the scarce resource here, LDS reads are cheap)
+// q B fragment of k-step ks (roped q of the group's four heads, bf16 in LDS: one 16-byte read
+// at each use: registers are the scarce resource here, LDS reads are cheap)
 template <int D>
-TTS_DEV bf16x8_t dec_qfrag(const float* qs, int lane, int ks) {
+TTS_DEV bf16x8_t dec_qfrag(const bf16_t* qs, int lane, int ks) {
   const int h = (lane & 15) & 3, g = lane >> 4;
-  const float4 a = *(const float4*)(qs + h * D + 32 * ks + 8 * g);
-  const float4 b = *(const float4*)(qs + h * D + 32 * ks + 8 * g + 4);
-  const u32x4_t w = {pack_bf2(a.x, a.y), pack_bf2(a.z, a.w), pack_bf2(b.x, b.y), pack_bf2(b.z, b.w)};
-  return __builtin_bit_cast(bf16x8_t, w);
+  return __builtin_bit_cast(bf16x8_t, *(const u32x4_t*)(qs + h * D + 32 * ks + 8 * g));
 }
 
-// S^T of one pass (scaled, positions >= ctx at -inf)
+// S^T of one pass (scaled, positions >= ctx at -inf).  tail (wave-uniform, dec_tail): the
+// wave's positions reach ctx - 1 or beyond; in every other wave the < ctx select is the identity.
 template <int D, int PW>
-TTS_DEV void dec_scores(const u32x4_t (&kf)[DecShape<D, PW>::MT][DecShape<D, PW>::KS], const float* qs,
-                        int base, int ctx, float scale, int lane, f32x4_t (&s)[DecShape<D, PW>::MT]) {
+TTS_DEV void dec_scores(const u32x4_t (&kf)[DecShape<D, PW>::MT][DecShape<D, PW>::KS], const bf16_t* qs,
+                        int base, int ctx, float scale, int lane, bool tail, f32x4_t (&s)[DecShape<D, PW>::MT]) {
   using C = DecShape<D, PW>;
   const int g = lane >> 4;
 #pragma unroll
@@ -177,7 +186,16 @@ TTS_DEV void dec_scores(const u32x4_t (&kf)[DecShape<D, PW>::MT][DecShape<D, PW>
 #pragma unroll
   for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) s[mt][r] = (dec_pos(base, mt, 4 * g + r) < ctx) ? s[mt][r] * scale : -INFINITY;
+    for (int r = 0; r < 4; ++r) s[mt][r] *= scale;
+  __builtin_amdgcn_sched_barrier(0);
+  if (tail) {
+#pragma unroll
+    for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s[mt][r] = (dec_pos(base, mt, 4 * g + r) < ctx) ? s[mt][r] : -INFINITY;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
 }
 
 // p = exp(s - M), l += p, O^T += V^T . P^T (bf16 P)
@@ -213,13 +231,13 @@ constexpr int dec_red_floats() { return NW * DEC_G * 2 + NW * DEC_G * D; }
 
 // The whole attention of one (row, kv head) by the NW waves of the workgroup (called by every
 // thread; contains barriers).  kf0 / vf0: this wave's pass-0 fragments, already issued (the
-// callers load them before anything else).  qs: roped q [4][D] fp32 (LDS, visible); knew /
+// callers load them before anything else).  qs: roped q [4][D] bf16 (LDS, visible); knew /
 // vnew: the new position's roped k and v (LDS bf16, visible).  out: the group's four heads'
 // output, bf16 [4][D] (row of attn_out at the group's first head).
 // (general form: `wave` / `tid` = this wave's / thread's index among the NW attending waves,
 // `bar` = a barrier over exactly those waves; dec_attend below: the whole workgroup)
 template <int D, int PW, int NW, class Bar, bool O32 = false>
-TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, float scale, const float* qs,
+TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, float scale, const bf16_t* qs,
                           const bf16_t* knew, const bf16_t* vnew, float* red,
                           u32x4_t (&kf0)[DecShape<D, PW>::MT][DecShape<D, PW>::KS],
                           u32x4_t (&vf0)[DecShape<D, PW>::PS][DecShape<D, PW>::DT], bf16_t* out, int wave,
@@ -238,10 +256,15 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   // kept; later passes (contexts beyond NW * PW positions) reload K only)
   f32x4_t s0[C::MT];
   float mx = -INFINITY;
+  const bool tail0 = dec_tail<PW>(base0, ctx);
   if (base0 < ctx) {
-    dec_patch_k<D, PW>(base0, ctx, lane, knew, kf0);
-    dec_patch_v<D, PW>(base0, ctx, lane, vnew, vf0);
-    dec_scores<D, PW>(kf0, qs, base0, ctx, scale, lane, s0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (tail0) {
+      dec_patch_k<D, PW>(base0, ctx, lane, knew, kf0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    dec_scores<D, PW>(kf0, qs, base0, ctx, scale, lane, tail0, s0);
 #pragma unroll
     for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
@@ -252,9 +275,15 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
     if (base >= ctx) break;
     u32x4_t kf[C::MT][C::KS];
     dec_load_k<D, PW, O32>(kc, base, ctx, lane, kf);
-    dec_patch_k<D, PW>(base, ctx, lane, knew, kf);
+    const bool tail = dec_tail<PW>(base, ctx);
+    __builtin_amdgcn_sched_barrier(0);
+    if (tail) {
+      dec_patch_k<D, PW>(base, ctx, lane, knew, kf);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
     f32x4_t s[C::MT];
-    dec_scores<D, PW>(kf, qs, base, ctx, scale, lane, s);
+    dec_scores<D, PW>(kf, qs, base, ctx, scale, lane, tail, s);
 #pragma unroll
     for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
@@ -263,6 +292,13 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   if (lane < DEC_G) mred[wave * DEC_G + lane] = mx;
+  // (the tail wave's V patch behind its maximum: the other waves wait for that at the barrier)
+  __builtin_amdgcn_sched_barrier(0);
+  if (base0 < ctx && tail0) {
+    dec_patch_v<D, PW>(base0, ctx, lane, vnew, vf0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
   bar();
   TTS_STAMP(stp, 5);
   float M = -INFINITY;
@@ -281,10 +317,20 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
     u32x4_t kf[C::MT][C::KS], vf[C::PS][C::DT];
     dec_load_v<D, PW, O32>(vtc, S, base, lane, vf);
     dec_load_k<D, PW, O32>(kc, base, ctx, lane, kf);
-    dec_patch_k<D, PW>(base, ctx, lane, knew, kf);
+    const bool tail = dec_tail<PW>(base, ctx);
+    __builtin_amdgcn_sched_barrier(0);
+    if (tail) {
+      dec_patch_k<D, PW>(base, ctx, lane, knew, kf);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
     f32x4_t s[C::MT];
-    dec_scores<D, PW>(kf, qs, base, ctx, scale, lane, s);
-    dec_patch_v<D, PW>(base, ctx, lane, vnew, vf);
+    dec_scores<D, PW>(kf, qs, base, ctx, scale, lane, tail, s);
+    if (tail) {
+      dec_patch_v<D, PW>(base, ctx, lane, vnew, vf);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
     dec_pv<D, PW>(M, lsum, s, vf, o);
   }
   lsum += __shfl_xor(lsum, 16, 64);
@@ -298,6 +344,7 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   }
   bar();
   TTS_STAMP(stp, 6);
+  static_assert(DEC_G * D <= NW * 64, "one output element per thread");
   bf16_t gob = 0;  // (granule output: this thread's element, i == tid: one iteration)
   for (int i = tid; i < DEC_G * D; i += NW * 64) {
     const int h = i / D, d = i - h * D;
@@ -315,18 +362,17 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
     out[h * D + d] = ob;
     if (gout) gob = ob;
   }
-  if (gout) {  // the row as granules: pairs (d, d + 1) through LDS (the partials are read)
-    bar();
-    if (tid < DEC_G * D) ((bf16_t*)ored)[tid] = gob;
-    bar();
-    if (tid < DEC_G * D / 2)
-      __hip_atomic_store(gout + tid, ((uint64_t)gtag << 32) | ((const uint32_t*)ored)[tid], __ATOMIC_RELAXED,
+  if (gout) {  // the row as granules: pairs (d, d + 1); the even lane takes d + 1 from its neighbour
+    // (quad_perm [1,0,3,2]: registers only; through LDS it was two barriers behind the combine)
+    const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)gob, 0xB1, 0xf, 0xf, false);
+    if (tid < DEC_G * D && !(tid & 1))
+      __hip_atomic_store(gout + (tid >> 1), ((uint64_t)gtag << 32) | (nb << 16) | gob, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
 template <int D, int PW, int NW, bool O32 = false>
-TTS_DEV void dec_attend(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, float scale, const float* qs,
+TTS_DEV void dec_attend(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, float scale, const bf16_t* qs,
                         const bf16_t* knew, const bf16_t* vnew, float* red,
                         u32x4_t (&kf0)[DecShape<D, PW>::MT][DecShape<D, PW>::KS],
                         u32x4_t (&vf0)[DecShape<D, PW>::PS][DecShape<D, PW>::DT], bf16_t* out,

@@ -39,7 +39,7 @@ __host__ __device__ inline int wgemm_red_floats(int waves, int ksplit, int ng, i
 constexpr int wgemm_fattn_d(int ku) { return ku == 2 ? 64 : 128; }
 template <int D>
 constexpr size_t fattn_lds_bytes() {
-  return (size_t)DEC_G * D * 4 + (DEC_G * D / 2 + D) * 4 + 2 * D * 2 + (size_t)dec_red_floats<D, DEC_NW>() * 4;
+  return (size_t)(DEC_G * D + 2 * D) * 2 + (size_t)dec_red_floats<D, DEC_NW>() * 4;
 }
 // A bounded granule wait: polls until `ready()` or `spins` polls; on timeout it sets the error
 // flag, and every later wait (this launch or the following ones) that finds the flag set
@@ -64,10 +64,8 @@ TTS_DEV void fattn_consumer(const WgemmArgs& wa, char* smem, int b) {
   constexpr int PW = dec_pw<D>(), G = DEC_G, H2 = D / 2;
   using C = DecShape<D, PW>;
   const AttnArgs& a = wa.fa;
-  float* qs = (float*)smem;                   // [G][D] roped q
-  uint32_t* raw = (uint32_t*)(qs + G * D);    // q pairs [G*D/2] | k pairs [D/2] | v pairs [D/2]
-  const bf16_t* rawb = (const bf16_t*)raw;
-  bf16_t* knew = (bf16_t*)(raw + G * D / 2 + D);
+  bf16_t* qs = (bf16_t*)smem;  // [G][D] roped q | roped new k [D] | new v [D], as bf16 pairs
+  bf16_t* knew = qs + G * D;
   bf16_t* vnew = knew + D;
   float* red = (float*)(vnew + D);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -81,15 +79,22 @@ TTS_DEV void fattn_consumer(const WgemmArgs& wa, char* smem, int b) {
   TTS_STAMP(stp, 0);
   u32x4_t kf[C::MT][C::KS], vf[C::PS][C::DT];
   if (wave * PW < ctx) {
-    dec_load_k<D, PW>(kc, wave * PW, ctx, lane, kf);
-    dec_load_v<D, PW>(vtc, a.max_seq, wave * PW, lane, vf);
+    dec_load_k<D, PW, D == 128>(kc, wave * PW, ctx, lane, kf);
+    dec_load_v<D, PW, D == 128>(vtc, a.max_seq, wave * PW, lane, vf);
   }
-  const int qd = tid % D;
-  const float qc = bf2f(a.rope_cos[(size_t)pos * D + qd]), qsn = bf2f(a.rope_sin[(size_t)pos * D + qd]);
+  // Thread tid < ngr takes granule tid of the group: q pairs [G*D/2] | k pairs [D/2] | v pairs
+  // [D/2], i.e. elements (d, d + 1), d = 2 tid mod D, of a q head / the new k / the new v.  The
+  // rotate_half partners of a pair are the pair D/4 granules away in the same head, hence in
+  // the same wave (a head is 32 lanes at D 64, 64 at D 128): the polling threads rope in
+  // registers.  The cos / sin of both dimensions are loaded before the wait.
+  const int qd = (2 * tid) % D;
+  const uint32_t cs2 = *(const uint32_t*)(a.rope_cos + (size_t)pos * D + qd);
+  const uint32_t sn2 = *(const uint32_t*)(a.rope_sin + (size_t)pos * D + qd);
 
   // wait for the projection's granules of this kv group: q of its G heads, the new k and v
   const uint32_t tag = ((uint32_t)pos << 6) | (uint32_t)wa.fattn_layer;
   const int nq = G * D / 2, ngr = nq + D;
+  uint32_t raw = 0;
   if (tid < ngr) {
     int col;
     if (tid < nq) col = kvh * G * D + 2 * tid;
@@ -101,22 +106,26 @@ TTS_DEV void fattn_consumer(const WgemmArgs& wa, char* smem, int b) {
       v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       return (uint32_t)(v >> 32) == tag;
     }, wa.fattn_err, wa.fattn_spins, true);
-    raw[tid] = (uint32_t)v;
+    raw = (uint32_t)v;
   }
-  lds_barrier();
+#ifdef TTS_STAMPS
+  lds_barrier();  // (diagnostic build only: stamp 1 = every thread's granule seen)
+#endif
   TTS_STAMP(stp, 1);
-  // RoPE of the group's q heads and of the new k (HF apply_rotary_pos_emb in bf16)
-  if (tid < G * D) {
-    const int g = tid / D;
-    qs[tid] = rope_elem(rawb[tid], rawb[g * D + (qd < H2 ? qd + H2 : qd - H2)], qd < H2, qc, qsn);
-  } else if (tid < G * D + D) {
-    const int d = tid - G * D;
-    knew[d] = f2bf(rope_elem(rawb[G * D + d], rawb[G * D + (d < H2 ? d + H2 : d - H2)], d < H2, qc, qsn));
-    vnew[d] = rawb[G * D + D + d];
+  // RoPE of the group's q heads and of the new k (HF apply_rotary_pos_emb in bf16); v as it is
+  const uint32_t rawr = (uint32_t)__shfl_xor((int)raw, D / 4, 64);
+  if (tid < ngr) {
+    uint32_t w = raw;
+    if (tid < nq + D / 2) {
+      const bool lower = qd < H2;
+      w = pack_bf2(rope_elem((bf16_t)raw, (bf16_t)rawr, lower, bf_lo(cs2), bf_lo(sn2)),
+                   rope_elem((bf16_t)(raw >> 16), (bf16_t)(rawr >> 16), lower, bf_hi(cs2), bf_hi(sn2)));
+    }
+    ((uint32_t*)qs)[tid] = w;  // (qs | knew | vnew are contiguous, in granule order)
   }
   lds_barrier();
   TTS_STAMP(stp, 2);
-  dec_attend<D, PW, DEC_NW>(kc, vtc, a.max_seq, ctx, a.scale, qs, knew, vnew, red, kf, vf,
+  dec_attend<D, PW, DEC_NW, D == 128>(kc, vtc, a.max_seq, ctx, a.scale, qs, knew, vnew, red, kf, vf,
                             a.out + (size_t)row * a.H * D + kvh * G * D, stp,
                             wa.fo_units ? wa.gran + (size_t)wa.M * (wa.N / 2) + (size_t)row * (a.H * D / 2) + kvh * G * D / 2
                                         : nullptr,

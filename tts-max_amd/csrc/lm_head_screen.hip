@@ -436,7 +436,9 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
     const unsigned long long old =
         __hip_atomic_fetch_max(a.lbg + tid * 8 + shard, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long cur = old > mine ? old : mine;
-    LBc[tid] = key2f((uint32_t)cur);  // (cur's step is this one: mine is, and nothing later exists)
+    // (a slot of another step, e.g. one left from before the 32-bit step counter wrapped, is
+    // not this step's bound: then only this workgroup's own value counts)
+    LBc[tid] = (cur >> 32) == ep ? key2f((uint32_t)cur) : v;
   }
   __syncthreads();
   // Wait (bounded; a.spins = 0: not at all) until every workgroup of the launch has added its
