@@ -65,6 +65,39 @@ tts_status tts_debug_step_plan(const tts_lm_config* cfg, int32_t rows, int32_t n
 tts_status tts_op_rmsnorm(const void* x, const void* w, float eps, void* y, int32_t M, int32_t K,
                           void* stream);
 
+/* SpeechLM attention alone (lm_attn.hip; LlamaAttention.forward after the projections:
+ * apply_rotary_pos_emb in bf16, the KV cache append, GQA 4:1 causal SDPA).  Common arguments:
+ * qkv = bf16 rows [rows][ld_qkv] laid out q (H*D) | k (KVH*D) | v (KVH*D), ld_qkv >= (H + 2 KVH) D
+ * and a multiple of 8; kcache = K rows [n_slots][KVH][max_seq][D]; vtcache = V^T
+ * [n_slots][KVH] blocks of D x max_seq in tiles of 16 dimensions x 32 positions (element (d, p) at
+ * (((d / 16) * (max_seq / 32) + p / 32) * 16 + d % 16) * 32 + p % 32); rope_cos / rope_sin = bf16
+ * tables [max_seq][D]; out = bf16 [rows][H*D].  Rejected with an error and no launch: D not 64 or
+ * 128, H != 4 KVH, max_seq not a multiple of 64, a slot outside [0, n_slots) or used by two rows /
+ * sequences, a position >= max_seq.
+ *
+ * Prefill: n_seq sequences (host arrays seq_slot, seq_pos0, seq_len); sequence b's seq_len[b]
+ * consecutive qkv rows are positions seq_pos0[b] .. + seq_len[b] - 1 of slot seq_slot[b]
+ * (seq_pos0 > 0: positions below it are already in the cache).  Runs the engine's RoPE + append
+ * launch (roped q -> q_rot [rows][H*D], roped k and v into the caches), then its causal
+ * attention launch over 16-row query blocks built as the engine builds them.  KVH <= 8.
+ * Returns after the stream has drained. */
+tts_status tts_op_attn_prefill(const void* qkv, int32_t ld_qkv, const int32_t* seq_slot, const int32_t* seq_pos0,
+                               const int32_t* seq_len, int32_t n_seq, int32_t n_slots, void* kcache,
+                               void* vtcache, int32_t max_seq, const void* rope_cos, const void* rope_sin,
+                               int32_t H, int32_t KVH, int32_t D, float scale, void* q_rot, void* out,
+                               void* stream);
+
+/* Decode step: row r (device int32 arrays row_slot, row_pos) is the new position row_pos[r] of
+ * slot row_slot[r]; it attends positions 0 .. row_pos[r] (the earlier ones from the caches, its
+ * own from the row) and is appended to the caches.  The rows come from qkv, or (qkv NULL) from
+ * qkv_part = fp32 partials [qkv_nsl][rows][ld_qkv] of a K-sliced projection, summed in slice
+ * order and rounded once to bf16. */
+tts_status tts_op_attn_decode(const void* qkv, const float* qkv_part, int32_t qkv_nsl, int32_t ld_qkv,
+                              int32_t rows, const int32_t* row_slot, const int32_t* row_pos, int32_t n_slots,
+                              void* kcache, void* vtcache, int32_t max_seq, const void* rope_cos,
+                              const void* rope_sin, int32_t H, int32_t KVH, int32_t D, float scale, void* out,
+                              void* stream);
+
 /* fp32 GEMM on the codec path: C[M][N] = act(A[M][K] . B[N][K]^T + bias) (+ resid).
  * lda may be < K to express a sliding-window (im2col-free) conv operand.  act: 0 none,
  * 1 swish, 2 silu (same function), see codec_gemm.hip. */

@@ -38,6 +38,35 @@ def test_abi_version_and_error_path():
     assert b"null" in lib.tts_last_error()
 
 
+def test_attention_ops_reject_unsupported_shapes_before_any_gpu_call():
+    """tts_op_attn_prefill / tts_op_attn_decode check the geometry on the host first: head dim
+    64 or 128, H = 4 KVH, at most 8 kv heads (prefill), max_seq a multiple of 64, ld_qkv wide
+    enough.  (The pointers are never dereferenced; the position checks need the device arrays:
+    tests/test_gpu_attn_ops.py.)"""
+    from tts_amd import _lib
+
+    lib = _lib.load_library()
+    p = 0x1000
+    one = (ctypes.c_int32 * 1)(0)
+    length = (ctypes.c_int32 * 1)(3)
+
+    def prefill(ld, max_seq, H, KVH, D):
+        return lib.tts_op_attn_prefill(p, ld, one, one, length, 1, 1, p, p, max_seq, p, p, H, KVH, D, 0.125, p, p, None)
+
+    def decode(ld, max_seq, H, KVH, D):
+        return lib.tts_op_attn_decode(p, None, 0, ld, 1, p, p, 1, p, p, max_seq, p, p, H, KVH, D, 0.125, p, None)
+
+    for fn in (prefill, decode):
+        for args, word in (((768, 64, 8, 2, 96), b"head dim"), ((768, 64, 6, 2, 64), b"num_heads"),
+                           ((768, 100, 8, 2, 64), b"max_seq"), ((760, 64, 8, 2, 64), b"ld_qkv")):
+            assert fn(*args) != 0, args
+            assert word in lib.tts_last_error(), (args, lib.tts_last_error())
+    assert prefill(54 * 64, 64, 36, 9, 64) != 0
+    assert b"8 kv heads" in lib.tts_last_error()
+    assert lib.tts_op_attn_decode(p, p, 4, 768, 1, p, p, 1, p, p, 64, p, p, 8, 2, 64, 0.125, p, None) != 0
+    assert b"exactly one" in lib.tts_last_error()
+
+
 def test_struct_layouts_match_header():
     from tts_amd import _lib
 

@@ -5,7 +5,11 @@ build of the commit before the tail of the core was trimmed (the file says how).
 
 The cases: the tail wave moving across a wave boundary and ending exactly on one, a second
 pass, a context below one wave, rows with different tails in the 2..16-row fused launch, the
-standalone kernel at 17 rows, and head dim 128 across its 512-position pass and at one row."""
+standalone kernel at 17 rows, and head dim 128 across its 512-position pass and at one row.
+
+The md5 is a change detector: it pins the core to its own earlier bits.  That those bits are
+RIGHT is checked by tests/test_gpu_attn_ops.py, which runs the attention kernels alone against
+the float64 reference of oracle/attn_oracle.py."""
 
 import json
 import os

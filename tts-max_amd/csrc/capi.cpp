@@ -432,6 +432,101 @@ tts_status tts_op_rmsnorm(const void* x, const void* w, float eps, void* y, int3
   });
 }
 
+// What the attention kernels support (lm_attn.hip): checked before any launch.
+static AttnArgs attn_op_args(const void* qkv, int32_t ld_qkv, int32_t n_slots, void* kcache, void* vtcache,
+                             int32_t max_seq, const void* rope_cos, const void* rope_sin, int32_t H,
+                             int32_t KVH, int32_t D, float scale, void* out) {
+  TTS_REQUIRE(kcache && vtcache && rope_cos && rope_sin && out, "null argument");
+  TTS_REQUIRE(D == 64 || D == 128, "head dim must be 64 or 128");
+  TTS_REQUIRE(KVH >= 1 && H == 4 * KVH, "num_heads must be 4 * num_kv_heads");
+  TTS_REQUIRE(max_seq >= 64 && max_seq % 64 == 0, "max_seq must be a multiple of 64");
+  TTS_REQUIRE((long long)max_seq * D < (1ll << 31), "max_seq * head_dim must be below 2^31");
+  TTS_REQUIRE(n_slots >= 1, "n_slots must be >= 1");
+  TTS_REQUIRE(ld_qkv >= (H + 2 * KVH) * D && ld_qkv % 8 == 0, "ld_qkv below (H + 2 KVH) D or not a multiple of 8");
+  AttnArgs a;
+  a.qkv = (const bf16_t*)qkv; a.ld_qkv = ld_qkv;
+  a.kcache = (bf16_t*)kcache; a.vtcache = (bf16_t*)vtcache; a.max_seq = max_seq;
+  a.rope_cos = (const bf16_t*)rope_cos; a.rope_sin = (const bf16_t*)rope_sin;
+  a.H = H; a.KVH = KVH; a.D = D; a.scale = scale;
+  a.out = (bf16_t*)out;
+  return a;
+}
+
+// every row's slot inside the cache and used once, every position inside the stride
+static void attn_op_check_rows(const std::vector<int>& slot, const std::vector<int>& last_pos, int n_slots,
+                               int max_seq) {
+  std::vector<char> used(n_slots, 0);
+  for (size_t i = 0; i < slot.size(); ++i) {
+    TTS_REQUIRE(slot[i] >= 0 && slot[i] < n_slots, "slot out of range");
+    TTS_REQUIRE(!used[slot[i]], "a slot appears twice");
+    used[slot[i]] = 1;
+    TTS_REQUIRE(last_pos[i] >= 0 && last_pos[i] < max_seq, "position out of range (>= max_seq)");
+  }
+}
+
+tts_status tts_op_attn_prefill(const void* qkv, int32_t ld_qkv, const int32_t* seq_slot, const int32_t* seq_pos0,
+                               const int32_t* seq_len, int32_t n_seq, int32_t n_slots, void* kcache,
+                               void* vtcache, int32_t max_seq, const void* rope_cos, const void* rope_sin,
+                               int32_t H, int32_t KVH, int32_t D, float scale, void* q_rot, void* out,
+                               void* stream) {
+  return guarded([&] {
+    TTS_REQUIRE(qkv && seq_slot && seq_pos0 && seq_len && q_rot && n_seq >= 1, "null argument");
+    AttnArgs a = attn_op_args(qkv, ld_qkv, n_slots, kcache, vtcache, max_seq, rope_cos, rope_sin, H, KVH, D,
+                              scale, out);
+    TTS_REQUIRE(KVH <= 8, "prefill: at most 8 kv heads");
+    std::vector<int> slot, pos, blk, sslot(seq_slot, seq_slot + n_seq), slast(n_seq);
+    int rows = 0;
+    for (int b = 0; b < n_seq; ++b) {
+      TTS_REQUIRE(seq_len[b] >= 1 && seq_pos0[b] >= 0 && seq_len[b] <= max_seq, "bad sequence length / first position");
+      slast[b] = seq_pos0[b] + seq_len[b] - 1;
+    }
+    attn_op_check_rows(sslot, slast, n_slots, max_seq);
+    for (int b = 0; b < n_seq; ++b) {
+      prefill_seq_rows(seq_slot[b], seq_pos0[b], seq_len[b], rows, slot, pos, blk);
+      rows += seq_len[b];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int* dev = nullptr;  // row_slot | row_pos | blocks (16-byte aligned: rows rounded up to 4)
+    const size_t r4 = ((size_t)rows + 3) / 4 * 4;
+    HIP_CHECK(hipMallocAsync((void**)&dev, (2 * r4 + blk.size()) * 4, s));
+    HIP_CHECK(hipMemcpyAsync(dev, slot.data(), (size_t)rows * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(dev + r4, pos.data(), (size_t)rows * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(dev + 2 * r4, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, s));
+    a.rows = rows; a.row_slot = dev; a.row_pos = dev + r4;
+    a.blocks = (const int4*)(dev + 2 * r4); a.nblocks = (int)blk.size() / 4;
+    a.q_rot = (bf16_t*)q_rot;
+    launch_rope_append(a, s);
+    launch_attn_prefill(a, s);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipFreeAsync(dev, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // (the host vectors above are the copies' sources)
+  });
+}
+
+tts_status tts_op_attn_decode(const void* qkv, const float* qkv_part, int32_t qkv_nsl, int32_t ld_qkv,
+                              int32_t rows, const int32_t* row_slot, const int32_t* row_pos, int32_t n_slots,
+                              void* kcache, void* vtcache, int32_t max_seq, const void* rope_cos,
+                              const void* rope_sin, int32_t H, int32_t KVH, int32_t D, float scale, void* out,
+                              void* stream) {
+  return guarded([&] {
+    TTS_REQUIRE(row_slot && row_pos && rows >= 1, "null argument");
+    TTS_REQUIRE((qkv != nullptr) != (qkv_part != nullptr), "exactly one of qkv and qkv_part");
+    TTS_REQUIRE(!qkv_part || qkv_nsl >= 1, "qkv_part needs qkv_nsl >= 1");
+    AttnArgs a = attn_op_args(qkv, ld_qkv, n_slots, kcache, vtcache, max_seq, rope_cos, rope_sin, H, KVH, D,
+                              scale, out);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> slot(rows), pos(rows);
+    HIP_CHECK(hipMemcpyAsync(slot.data(), row_slot, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(pos.data(), row_pos, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    attn_op_check_rows(slot, pos, n_slots, max_seq);
+    a.rows = rows; a.row_slot = row_slot; a.row_pos = row_pos;
+    a.qkv_part = qkv_part; a.qkv_nsl = qkv_part ? qkv_nsl : 0;
+    launch_attn_decode_step(a, s);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
 tts_status tts_op_gemm_f32(const float* A, int32_t M, int32_t K, int32_t lda, const float* B,
                            int32_t N, const float* bias, float* C, int32_t ldc,
                            const float* resid, int32_t act, void* stream) {

@@ -760,14 +760,9 @@ static void prefill_rows_setup(Ctx& X, const int32_t* ids, const int32_t* lens, 
   rows = 0;
   last_rows.resize(B);
   for (int b = 0; b < B; ++b) {
-    for (int i = 0; i < lens[b]; ++i) {
-      slot.push_back(slot_base + b);
-      pos.push_back(i);
-      tok.push_back(ids[rows + i]);
-    }
-    // attention query blocks: up to 16 consecutive rows of one sequence (lm_attn.hip)
-    for (int t0 = 0; t0 < lens[b]; t0 += 16)
-      blk.insert(blk.end(), {rows + t0, std::min(16, lens[b] - t0), slot_base + b, t0});
+    for (int i = 0; i < lens[b]; ++i) tok.push_back(ids[rows + i]);
+    // query rows and attention query blocks (up to 16 consecutive rows of one sequence)
+    prefill_seq_rows(slot_base + b, 0, lens[b], rows, slot, pos, blk);
     rows += lens[b];
     last_rows[b] = rows - 1;
   }

@@ -277,6 +277,18 @@ void launch_splitk_combine_norm(const float* part, int kc, int M, int N, int ldp
                                 const bf16_t* normw, float eps, bf16_t* xn, int ldn, hipStream_t s);
 
 // ---- attention (lm_attn.hip)
+// Prefill rows of one sequence: positions pos0 .. pos0 + len - 1 of KV slot `slot` become query
+// rows row0 .. row0 + len - 1 (appended to row_slot / row_pos) and query blocks of up to 16
+// consecutive rows (appended to blk as {first row, rows, slot, first position}, AttnArgs::blocks).
+inline void prefill_seq_rows(int slot, int pos0, int len, int row0, std::vector<int>& row_slot,
+                             std::vector<int>& row_pos, std::vector<int>& blk) {
+  for (int i = 0; i < len; ++i) {
+    row_slot.push_back(slot);
+    row_pos.push_back(pos0 + i);
+  }
+  for (int t0 = 0; t0 < len; t0 += 16)
+    blk.insert(blk.end(), {row0 + t0, len - t0 < 16 ? len - t0 : 16, slot, pos0 + t0});
+}
 void launch_rope_append(const AttnArgs& a, hipStream_t s);  // prefill: rope q, k; K rows, V columns
 void launch_attn_prefill(const AttnArgs& a, hipStream_t s);  // prefill: causal attention per query block
 // decode step: one workgroup per (row, kv head): RoPE, attention over pos + 1 positions,
