@@ -105,9 +105,11 @@ typedef struct {
  * engine-computed RoPE table (the Python host passes the table computed exactly as
  * LlamaRotaryEmbedding.forward does).  Optional "vocab.id_to_code" (int32 [vocab]) is the
  * token-id -> speech-code LUT (-1 for non-speech ids), see tts_lm_id_to_code.
- * Greedy steps pick through an int8 copy of the lm_head made here (vocab x hidden bytes more
- * device memory) — the same ids as the bf16 lm_head; TTS_HEAD_SCREEN=0 at load
- * skips it. */
+ * Greedy steps, and sampled steps of up to 16 rows (8 at hidden 4096) with top_k <= 64, pick
+ * through an int8 copy of the lm_head made here (vocab x hidden bytes more device memory, plus
+ * the sampled step's candidate lists: 8 bytes x vocab x min(max_batch, 16)) —
+ * the same ids as the bf16 lm_head, for sampled steps with the same seed; TTS_HEAD_SCREEN=0 at
+ * load skips it. */
 tts_status tts_lm_load(tts_engine* e, const tts_lm_config* cfg, const tts_tensor_desc* t,
                        int32_t n);
 
@@ -120,7 +122,8 @@ typedef struct {
   float repetition_penalty;    /* over the SET of ids in prompt+generated            */
   float temperature;           /* sampling only                                      */
   float top_p;                 /* sampling only                                      */
-  int32_t top_k;               /* sampling only (HF default 50); 0 = off             */
+  int32_t top_k;               /* sampling only (HF default 50), 1 .. 1024; <= 64: the  */
+                               /* step samples through the screened lm_head (<= 16 rows) */
   uint64_t seed;               /* sampling RNG seed                                  */
   float frequency_penalty;     /* vLLM form (inferencing.py:85): logit -= f * count of */
                                /* the id among the NEW tokens; 0 = off (HF form)       */
@@ -206,7 +209,10 @@ tts_status tts_lm_last_timing(tts_engine* e, float* prefill_ms, float* decode_ms
  * fused in (1..16 rows where that form applies), 7 the same launch also carrying o_proj
  * (+residual; the 1..16-row step's default form where the shapes allow), 8 the greedy step's
  * screened lm_head (int8 screen + exact recheck of the tiles that can hold the argmax; <= 32
- * rows), 9 its int8 screen alone.  rows = batch rows.
+ * rows), 9 its int8 screen alone, 10 the sampled step's screened head (temperature 0.8, top_k
+ * 50: the screen's top-k mode, its exact recompute and the list sampler; 1..16 rows, 1..8 at
+ * hidden 4096), 11 the full sampling head (the lm_head with its logits store + the dense
+ * sampler).  rows = batch rows.
  * Outputs: average ms per launch and the algorithmic HBM bytes one launch must move. */
 tts_status tts_lm_bench_kernel(tts_engine* e, int32_t which, int32_t rows, int32_t ctx,
                                int32_t iters, float* avg_ms, double* bytes);

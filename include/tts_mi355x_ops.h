@@ -53,6 +53,18 @@ tts_status tts_op_sample(const float* logits, int32_t B, int32_t V, float temper
                          float top_p, uint64_t seed, int32_t step, const float* part_max, int32_t nparts,
                          float* probs, int32_t* tokens, void* stream);
 
+/* The same draw from per-row candidate lists instead of dense rows (the screened sampled step's
+ * sampler, alone): row b is counts[b] (<= cap) entries scores[b][i] (processed fp32 logits) of
+ * the ids ids[b][i] (distinct, in [0, V)), rows `cap` entries apart; every id not listed counts
+ * as -inf.  A list that holds every entry of the row's top-k set gives the token and the probs
+ * (written into probs [B][V] at the kept ids; the caller zero-fills it) of tts_op_sample on the
+ * dense row, bit for bit.  Lists longer than the kernel's 2048 LDS candidates take the exact
+ * radix select over the list.  An empty list (counts[b] == 0) has nothing to draw from: token 0,
+ * no probs.  counts is only read. */
+tts_status tts_op_sample_list(const float* scores, const int32_t* ids, const int32_t* counts, int32_t B,
+                              int32_t cap, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                              int32_t step, float* probs, int32_t* tokens, void* stream);
+
 /* Diagnostics, no GPU needed: the kernels one decode step over `rows` rows of a model of
  * config `cfg` would launch on a GPU of `num_cu` CUs — the engine's own step code run with
  * its launchers in a dry-run mode (nothing allocated or launched).  Writes the unique launches
@@ -60,6 +72,11 @@ tts_status tts_op_sample(const float* logits, int32_t B, int32_t V, float temper
  * "wgemm_kernel<template arguments>"), NUL-terminated, into out[cap].  The build's spill gate
  * (tests/test_kernel_resources.py) reads its hot instantiations from here. */
 tts_status tts_debug_step_plan(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, char* out, int32_t cap);
+/* ... of a sampled step (do_sample at temperature 0.8, top_p 1.0 and the given top_k in [1, 1024]):
+ * the screened sampling head where it applies (head_screen_kernel<..., true> + sample_list_kernel),
+ * else the full lm_head with its logits store + sample_kernel. */
+tts_status tts_debug_step_plan_sampled(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t top_k,
+                                       char* out, int32_t cap);
 
 /* LlamaRMSNorm over rows of x (bf16). */
 tts_status tts_op_rmsnorm(const void* x, const void* w, float eps, void* y, int32_t M, int32_t K,

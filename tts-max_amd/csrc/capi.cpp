@@ -250,6 +250,17 @@ tts_status tts_debug_step_plan(const tts_lm_config* cfg, int32_t rows, int32_t n
   });
 }
 
+tts_status tts_debug_step_plan_sampled(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t top_k,
+                                       char* out, int32_t cap) {
+  return guarded([&] {
+    TTS_REQUIRE(cfg && out && cap > 0, "null argument");
+    TTS_REQUIRE(top_k >= 1 && top_k <= SAMPLE_MAX_TOP_K, "top_k in [1, 1024]");
+    const std::string p = lm_step_plan(*cfg, rows, num_cu, top_k);
+    TTS_REQUIRE((int64_t)p.size() < cap, "output buffer too small");
+    memcpy(out, p.c_str(), p.size() + 1);
+  });
+}
+
 tts_status tts_codec_load(tts_engine* e, const tts_codec_config* cfg, const tts_tensor_desc* t,
                           int32_t n) {
   return guarded([&] {
@@ -418,6 +429,23 @@ tts_status tts_op_sample(const float* logits, int32_t B, int32_t V, float temper
     a.part_val = part_max; a.nparts = part_max ? nparts : 0; a.part_stride = nparts;
     a.probs = probs; a.tokens = tokens;
     launch_sample(a, B, (hipStream_t)stream);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+tts_status tts_op_sample_list(const float* scores, const int32_t* ids, const int32_t* counts, int32_t B,
+                              int32_t cap, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                              int32_t step, float* probs, int32_t* tokens, void* stream) {
+  return guarded([&] {
+    TTS_REQUIRE(scores && ids && counts && tokens && B >= 1 && V >= 1 && cap >= 1, "bad arguments");
+    TTS_REQUIRE(temperature > 0.f && top_k >= 1 && top_k <= SAMPLE_MAX_TOP_K && top_p > 0.f && top_p <= 1.f,
+                "temperature > 0, top_k in [1, 1024], top_p in (0, 1]");
+    SampleArgs a;
+    a.logits = scores; a.list_idx = ids; a.list_cnt = const_cast<int32_t*>(counts);  // (list_clear 0: only read)
+    a.ldl = cap; a.V = cap; a.vocab = V;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.step0 = step;
+    a.probs = probs; a.tokens = tokens;
+    launch_sample_list(a, B, (hipStream_t)stream);
     HIP_CHECK(hipGetLastError());
   });
 }

@@ -93,6 +93,7 @@ struct LmWork {
   DevBuf epoch;                                     // decode-step counter (u32; the screened head's step keys)
   DevBuf lpart_v, lpart_i;                          // lm_head argmax partials
   DevBuf hub, hlb;                                  // screened head: check-mode score bounds [B][V], per-row max lower bound (u64)
+  DevBuf hslot, hcv, hci, hcn, hlo;                 // sampled screened head: workgroup slots (u64), candidate scores / ids [16][V], counts, check-mode lower bounds
   DevBuf hxq, hxs;                                  // screened head at 17..32 rows: the rows quantised [2B][hidden] i8, their stats
   DevBuf kpart;                                     // K-sliced GEMM fp32 partials [kc][rows][N]
   DevBuf ppart;                                     // prefill GEMM fp32 partials [chunks][rows][N] (lm_pgemm.hip)
@@ -171,7 +172,7 @@ void lm_score_decode(Engine* e, const int32_t* ids, const int32_t* lens, int B, 
                      const int32_t* gidx, int k, float* out, hipStream_t s);
 void lm_bench_kernel(Engine* e, int which, int rows, int ctx, int iters, float* avg_ms,
                      double* bytes);
-std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu);
+std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k = 0);  // top_k > 0: a sampled step
 
 // upload a named tensor to device memory as bf16 (convert from f32 if needed)
 void upload_bf16(const tts_tensor_desc& d, bf16_t* dst, hipStream_t s, DevBuf& staging);

@@ -31,14 +31,18 @@ static bool head_screen_enabled() {
   return v;
 }
 // ... whose workgroups wait for every workgroup's bounds before flagging their units (the
-// exact candidate set; TTS_HEAD_SCREEN_WAIT=0: never, 1: always, n > 1 (default 2): from n rows —
-// one row: 69 vs 73 us, 8 rows: 79 vs 96 us without, profiles/r6w_ab_head_wait_*).  Same bits
-// either way: a lower LB only flags more units
-static bool head_screen_wait(int rows) {
-  static const int v = getenv("TTS_HEAD_SCREEN_WAIT") ? atoi(getenv("TTS_HEAD_SCREEN_WAIT")) : 2;
+// exact candidate set; TTS_HEAD_SCREEN_WAIT=0: never, 1: always, n > 1: from n rows; unset: greedy
+// steps from 2 rows — one row: 69 vs 73 us, 8 rows: 79 vs 96 us without,
+// profiles/r6w_ab_head_wait_* — and sampled steps always: their threshold is the k-th largest of
+// the workgroups' slots, and a workgroup that sees fewer than k of them recomputes all of its
+// units).  Same bits either way: a lower bound only flags more units
+static bool head_screen_wait(int rows, bool sampled = false) {
+  static const int v = getenv("TTS_HEAD_SCREEN_WAIT") ? atoi(getenv("TTS_HEAD_SCREEN_WAIT")) : -1;
+  if (v < 0) return sampled || rows >= 2;
   return v == 1 || (v > 1 && rows >= v);
 }
 // TTS_HEAD_SCREEN_CHECK=1: every unit recomputed and each exact score checked against its bound
+// (greedy: the upper one, which the argmax depends on; sampled: both)
 static bool head_screen_check() {
   static const bool v = getenv("TTS_HEAD_SCREEN_CHECK") && atoi(getenv("TTS_HEAD_SCREEN_CHECK"));
   return v;
@@ -315,8 +319,20 @@ void lm_load(Engine* e, const tts_lm_config* cfgp, const tts_tensor_desc* t, int
     w.hxs.alloc((size_t)32 * 16);
     w.hlb.alloc(32 * 8 * 8 + 8 * 64);  // 32 rows x 8 shards of bounds + 8 arrival counters (64 B apart)
     HIP_CHECK(hipMemsetAsync(w.hlb.p, 0, w.hlb.bytes, s));  // (below any step's key)
+    // the sampled step (1..16 rows): a slot per (row, workgroup), the candidate lists (capacity V a
+    // row: they cannot overflow) and their counts (zero between steps: the sampler clears them)
+    const int SB = std::min(B, 16);
+    w.hslot.alloc((size_t)16 * 512 * 8);
+    HIP_CHECK(hipMemsetAsync(w.hslot.p, 0, w.hslot.bytes, s));
+    w.hcv.alloc((size_t)SB * V * 4);
+    w.hci.alloc((size_t)SB * V * 4);
+    w.hcn.alloc(64);
+    HIP_CHECK(hipMemsetAsync(w.hcn.p, 0, 64, s));
+    if (head_screen_check()) w.hlo.alloc((size_t)SB * V * 4);
+    else w.hlo.release();
   } else {
     w.hub.release(); w.hlb.release(); w.hxq.release(); w.hxs.release();
+    w.hslot.release(); w.hcv.release(); w.hci.release(); w.hcn.release(); w.hlo.release();
   }
   w.row_slot.alloc((size_t)R * 4);
   w.row_pos.alloc((size_t)R * 4);
@@ -668,11 +684,24 @@ struct Ctx {
     return st;
   }
 
+  // the sampled step through the screen: the int8 copy exists, the rows and top_k are covered
+  // (every covered row count measured faster than the full head: DESIGN.md 3.6, no row gate)
+  bool sampled_screen_ok(int B, const tts_gen_params& gp) const {
+    return gp.do_sample && M.head_grid &&
+           head_screen_topk_supported(B, c.hidden_size, c.vocab_size, gp.top_k, M.head_grid);
+  }
+
   // lm_head over B rows of `xin` + the pick (greedy argmax, or the sampling head) + finalize
   // (state update, next embedding -> w.x)
   void head_and_pick(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp) {
     if (!gp.do_sample && M.head_grid && head_screen_supported(B, c.hidden_size, c.vocab_size)) {
       screened_head(xin, B, st, gp);
+      return;
+    }
+    if (sampled_screen_ok(B, gp)) {
+      screened_sample(xin, B, st, gp);
+      launch_finalize_greedy(w.lpart_v.as<float>(), w.lpart_i.as<int>(), LOGITS_MAX_PARTS, 1, st, B,
+                             M.embed_rows.as<bf16_t>(), w.x.as<bf16_t>(), c.hidden_size, s);
       return;
     }
     WgemmArgs ex;
@@ -708,9 +737,25 @@ struct Ctx {
     launch_finalize_greedy(w.lpart_v.as<float>(), w.lpart_i.as<int>(), LOGITS_MAX_PARTS, rg, st, B,
                            M.embed_rows.as<bf16_t>(), w.x.as<bf16_t>(), c.hidden_size, s);
   }
+  // the sampled pick through the same screen (its top-k mode): the candidates of the top-k set,
+  // recomputed exactly, into per-row lists; the list sampler draws from them and leaves the token
+  // as the one "partial" finalize reads.  The ids of the full-head sampled step.
+  void screened_sample(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp) {
+    screened_head_parts(xin, B, st, gp, gp.top_k);
+    SampleArgs sa;
+    sa.logits = w.hcv.as<float>(); sa.list_idx = w.hci.as<int>(); sa.list_cnt = w.hcn.as<int>();
+    sa.list_clear = 1;
+    sa.ldl = c.vocab_size; sa.V = c.vocab_size; sa.vocab = c.vocab_size;
+    sa.temperature = gp.temperature; sa.top_k = gp.top_k; sa.top_p = gp.top_p;
+    sa.seed = gp.seed; sa.row_seed = st.row_seed; sa.step = st.gen_count; sa.done = st.done;
+    sa.part_stride = LOGITS_MAX_PARTS;
+    sa.out_part_val = w.lpart_v.as<float>(); sa.out_part_idx = w.lpart_i.as<int>();
+    launch_sample_list(sa, B, s);
+  }
   // the screened head's launch (int8 screen + exact recompute of the units that can hold the
-  // argmax); returns the number of argmax partials per row
-  int screened_head_parts(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp) {
+  // argmax); returns the number of argmax partials per row.  top_k > 0: its top-k mode (the
+  // units that can hold a top-k candidate, into the candidate lists; no argmax partials)
+  int screened_head_parts(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp, int top_k = 0) {
     const int HID = c.hidden_size, V = c.vocab_size;
     HeadScreenArgs a;
     a.M = B; a.K = HID; a.ldx = HID; a.V = V;
@@ -736,10 +781,16 @@ struct Ctx {
     a.eos_mask = st.eos_mask; a.counts = st.counts; a.freq_penalty = gp.frequency_penalty;
     a.epoch = st.epoch; a.lbg = w.hlb.as<unsigned long long>();
     a.arrive = (uint32_t*)(w.hlb.as<unsigned long long>() + 32 * 8);
-    a.spins = head_screen_wait(B) ? (1 << 14) : 0;
+    a.spins = head_screen_wait(B, top_k > 0) ? (1 << 14) : 0;
     a.part_val = w.lpart_v.as<float>(); a.part_idx = w.lpart_i.as<int>(); a.part_stride = LOGITS_MAX_PARTS;
     if (head_screen_check()) {
       a.check = 1; a.ub = w.hub.as<float>(); a.ldu = V; a.err = w.ferr.as<int>() + 1;
+    }
+    if (top_k > 0) {
+      a.top_k = top_k;
+      a.slots = w.hslot.as<unsigned long long>();
+      a.cand_val = w.hcv.as<float>(); a.cand_idx = w.hci.as<int>(); a.cand_cnt = w.hcn.as<int>(); a.ldc = V;
+      if (a.check) a.lbo = w.hlo.as<float>();
     }
     static const int diag = getenv("TTS_HEAD_SCREEN_DIAG") ? atoi(getenv("TTS_HEAD_SCREEN_DIAG")) : 0;
     a.diag = diag;
@@ -974,7 +1025,7 @@ static void check_fattn(Engine* e, hipStream_t s) {
     HIP_CHECK(hipMemsetAsync(e->w.ferr.p, 0, 8, s));
     HIP_CHECK(hipStreamSynchronize(s));
     TTS_REQUIRE(!err[0], "fused QKV+attention: a granule wait timed out (results invalid)");
-    TTS_REQUIRE(false, "screened lm_head: an exact score above its int8 bound (TTS_HEAD_SCREEN_CHECK)");
+    TTS_REQUIRE(false, "screened lm_head: an exact score outside its int8 bound (TTS_HEAD_SCREEN_CHECK)");
   }
 }
 
@@ -1178,10 +1229,13 @@ void lm_bench_kernel(Engine* e, int which, int rows, int ctx, int iters, float* 
   TTS_REQUIRE(e->lm.loaded, "tts_lm_load has not been called");
   TTS_REQUIRE(rows >= 1 && rows <= e->w.cap_batch, "rows out of range");
   TTS_REQUIRE(ctx >= 1 && ctx <= e->lm.cfg.max_seq_len, "ctx out of range");
-  TTS_REQUIRE(which >= 0 && which <= 9 && iters >= 1, "bad kernel selector");
+  TTS_REQUIRE(which >= 0 && which <= 11 && iters >= 1, "bad kernel selector");
   TTS_REQUIRE(which < 6 || which > 7 || Ctx(e, e->stream).fused_attn_ok(rows, true),
               "fused QKV+attention does not apply to this shape");
-  TTS_REQUIRE(which < 8 || (e->lm.head_grid && rows <= 32 && head_screen_supported(rows, e->lm.cfg.hidden_size,
+  TTS_REQUIRE(which != 10 || (e->lm.head_grid && head_screen_topk_supported(rows, e->lm.cfg.hidden_size, e->lm.cfg.vocab_size,
+                                                                              50, e->lm.head_grid)),
+              "the screened sampling head does not apply to this shape (or is off)");
+  TTS_REQUIRE(which < 8 || which > 9 || (e->lm.head_grid && rows <= 32 && head_screen_supported(rows, e->lm.cfg.hidden_size,
                                                                                       e->lm.cfg.vocab_size)),
               "the screened lm_head does not apply to this shape (or is off)");
   TTS_REQUIRE(which != 7 || (rows == 1 ? Ctx(e, e->stream).fused_oproj_ok() : Ctx(e, e->stream).fused_oproj_rows_ok(rows)),
@@ -1267,6 +1321,34 @@ void lm_bench_kernel(Engine* e, int which, int rows, int ctx, int iters, float* 
         // int8 matrix + per-column constants + rows + penalty bits (+ the recomputed units' bf16 tiles,
         // a few dozen of 64 KiB, not counted)
         b = (double)V * HID + 16.0 * V + act_rw * HID + rows * (V / 8.0);
+        break;
+      }
+      case 10:    // the sampled step's screened head: screen + exact recompute + the list sampler
+      case 11: {  // today's sampling head: the lm_head with the logits store + the dense sampler
+        tts_gen_params gp{};
+        gp.repetition_penalty = 1.1f;
+        gp.do_sample = 1; gp.temperature = 0.8f; gp.top_k = 50; gp.top_p = 1.0f;
+        if (which == 10) {
+          X.pending_norm = nullptr;
+          X.screened_sample(e->w.x.as<bf16_t>(), rows, st, gp);
+          // (+ the recomputed units' bf16 tiles and the candidate lists, not counted)
+          b = (double)V * HID + 16.0 * V + act_rw * HID + rows * (V / 8.0);
+        } else {
+          WgemmArgs sx = ex;
+          sx.logits_out = e->w.slogits.as<float>(); sx.ldl = V;
+          X.gemm(e->w.x.as<bf16_t>(), rows, HID, X.M.lm_head, V, X.M.final_norm, nullptr, 0, nullptr, EPI_LOGITS, &sx);
+          SampleArgs sa;
+          sa.logits = sx.logits_out; sa.ldl = V; sa.V = V;
+          sa.temperature = gp.temperature; sa.top_k = gp.top_k; sa.top_p = gp.top_p;
+          sa.row_seed = st.row_seed; sa.step = st.gen_count; sa.done = st.done;
+          sa.part_val = sx.part_val; sa.nparts = plan_wgemm(rows, V, HID, EPI_LOGITS, e->num_cu).grid;
+          sa.part_stride = LOGITS_MAX_PARTS;
+          sa.tokens = e->w.row_idx.as<int>();  // (not the partials: the next launch's bound reads them)
+          launch_sample(sa, rows, s);
+          // the logits written once and read once by the sampler
+          b = 2.0 * V * HID + act_rw * HID + 2.0 * HID + rows * (V / 8.0) + 2.0 * rows * V * 4.0;
+        }
+        launch_bump_epoch(st.epoch, s);
         break;
       }
     }
@@ -1406,7 +1488,7 @@ void lm_score_decode(Engine* e, const int32_t* ids, const int32_t* lens, int B, 
 // without a GPU: the step's own code (Ctx::layers + head_and_pick) run with the launchers in
 // dry-run mode (lm_kernels.h dry_launches), nothing allocated.  Unique launches in first-seen
 // order, one per line (wgemm instantiations as wgemm_inst_name writes them).
-std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu) {
+std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k) {
   TTS_REQUIRE(c.head_dim == 64 || c.head_dim == 128, "head_dim must be 64 or 128");
   TTS_REQUIRE(c.num_heads == 4 * c.num_kv_heads && c.num_layers >= 1, "bad config");
   TTS_REQUIRE(rows >= 1 && rows <= 64 && num_cu >= 1, "rows in [1, 64], num_cu >= 1");
@@ -1439,6 +1521,9 @@ std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu) {
     const StepState st = X.state(rows, 0, 0);
     tts_gen_params gp{};
     gp.repetition_penalty = 1.1f;
+    if (top_k > 0) {  // a sampled step
+      gp.do_sample = 1; gp.temperature = 0.8f; gp.top_k = top_k; gp.top_p = 1.0f;
+    }
     X.head_and_pick(nullptr, rows, st, gp);
   } catch (...) {
     dry_launches() = nullptr;

@@ -27,9 +27,17 @@
 //
 // So the chosen id is bit-for-bit the full lm_head's (tests/test_gpu_head_screen.py, and every
 // greedy parity test runs through this path), whatever the weights: a loose bound only costs
-// more recomputed tiles (all of them at worst).  Sampling (do_sample) needs every processed logit
-// and keeps the full lm_head.  TTS_HEAD_SCREEN=0: the full lm_head for greedy steps too;
-// TTS_HEAD_SCREEN_CHECK=1: every tile recomputed and checked against its bound (tests).
+// more recomputed tiles (all of them at worst).
+//
+// Sampling (do_sample) always cuts at a top_k in [1, 1024], so it needs only the top-k set of the
+// processed scores: the kernel's TOPK mode (see the kernel's comment) flags the units against a
+// lower bound T of the k-th largest score and appends every exact (score, id) >= T to a per-row
+// candidate list that sample_list_kernel (lm_sample.hip) draws from: the ids of the full-head
+// sampled step, bit for bit, with the same seed.  Covered: 1..16 rows at K 2048, 1..8 at K 4096,
+// top_k <= HEAD_SCREEN_MAX_TOP_K (64); anything else samples over the full lm_head.
+// TTS_HEAD_SCREEN=0: the full lm_head for every step;
+// TTS_HEAD_SCREEN_CHECK=1: every tile recomputed and checked against its bound (tests; the
+// sampled mode checks both sides, lb <= s <= ub).
 #include <math.h>
 
 #include "hip_common.h"
@@ -232,8 +240,21 @@ TTS_DEV float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k 
 // PRE (17..32 rows): the rows come normalised (a.x) and quantised by head_rowquant_kernel (a.xq,
 // a.xstat: one pass instead of every workgroup quantising every row); the recompute then reads
 // its A fragments from a.x (L2) instead of an LDS copy, and the int8 image takes the LDS
-template <int MT, int KT8, int RPW, bool PRE>
+//
+// TOPK (the sampled step, 1..16 rows): the same screen picks the candidates of the top-k set
+// instead of the argmax.  Every workgroup publishes its per-row maximum of lb in a slot of its own
+// ((decode step << 32) | order key, as the shards above: a slot of an earlier step is not
+// counted); the slots cover disjoint columns, so the k-th largest of any of them, T, is at most
+// the k-th largest exact score, and every column TopKLogitsWarper keeps (ties at the k-th value
+// included) has ub >= s >= T.  After the same bounded wait each workgroup takes T from the slots
+// of this step it can see (fewer than k: T = -inf, every unit flagged: slow, exact), flags its
+// units against T, recomputes them exactly and appends every (score, id) with score >= T to the
+// row's candidate list (capacity V: a column is appended at most once; the count is zeroed by the
+// list's reader, sample_list_kernel).  The list holds the whole top-k set, so the sampler's sort
+// and cut give the dense row's draw.  Workgroups may use different T: each is a valid bound.
+template <int MT, int KT8, int RPW, bool PRE, bool TOPK = false>
 __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenArgs a) {
+  static_assert(!(PRE && TOPK), "the top-k mode covers the non-prequantised forms");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int K = KT8 * 64, ldA = K + 16, ldX = K + 8, KU = kScrKU, R = kScrR, S = KT8 / KU, CPL = K / 512;
   constexpr int MMAX = 8 * MT;  // rows of the int8 image (two A rows each)
@@ -404,6 +425,9 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
           const float lb =
               head_proc_bound<false>(rbf(av - e), sw[mt][p], c, a.penalty, inv_pen, crow, a.freq_penalty, eosr[mt][p]);
           if (a.ub) a.ub[(size_t)m * a.ldu + c] = ub;  // (check mode)
+          if constexpr (TOPK) {
+            if (a.lbo) a.lbo[(size_t)m * a.ldu + c] = lb;
+          }
           lbm[mt][p] = fmaxf(lbm[mt][p], lb);
         }
         // the unit's maximum of ub per row (its 16 columns = the 16 lanes of the group)
@@ -433,12 +457,19 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
 #pragma unroll
     for (int w = 1; w < kScrWaves; ++w) v = fmaxf(v, rlb[w * MMAX + tid]);
     const unsigned long long mine = (ep << 32) | f2key(v);
-    const unsigned long long old =
-        __hip_atomic_fetch_max(a.lbg + tid * 8 + shard, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long cur = old > mine ? old : mine;
-    // (a slot of another step, e.g. one left from before the 32-bit step counter wrapped, is
-    // not this step's bound: then only this workgroup's own value counts)
-    LBc[tid] = (cur >> 32) == ep ? key2f((uint32_t)cur) : v;
+    if constexpr (TOPK) {
+      // this workgroup's own slot (a maximum, as the shards: an earlier step's value loses; one
+      // left from before the step counter wrapped wins and the slot then counts for nothing)
+      __hip_atomic_fetch_max(a.slots + (size_t)tid * gridDim.x + blockIdx.x, mine, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      const unsigned long long old =
+          __hip_atomic_fetch_max(a.lbg + tid * 8 + shard, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long cur = old > mine ? old : mine;
+      // (a slot of another step, e.g. one left from before the 32-bit step counter wrapped, is
+      // not this step's bound: then only this workgroup's own value counts)
+      LBc[tid] = (cur >> 32) == ep ? key2f((uint32_t)cur) : v;
+    }
   }
   __syncthreads();
   // Wait (bounded; a.spins = 0: not at all) until every workgroup of the launch has added its
@@ -465,7 +496,43 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
     }
   }
   __syncthreads();
-  if (tid < M * 8) {  // (also without the wait: the other shards' maxima so far cut the recompute,
+  if constexpr (TOPK) {
+    // T[m] = the k-th largest of this step's slots (wave w: rows w, w + 4, ...; a lane holds slots
+    // lane, lane + 64, ...: host-checked grid <= 512), by a radix select over the order keys, most
+    // significant bit first (wave ballots); fewer than k slots of this step: -inf
+    const int G = gridDim.x, nj = (G + 63) >> 6;
+    for (int m = wave; m < M; m += kScrWaves) {
+      uint32_t key[8];
+      int valid = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        key[j] = 0u;
+        if (j < nj) {  // (wave-uniform)
+          const int i = lane + 64 * j;
+          unsigned long long cur = 0ull;
+          if (i < G) cur = __hip_atomic_load(a.slots + (size_t)m * G + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          // (order key 0 is no bound's key — f2key(-inf) is 0x007fffff — but it is what a slot
+          // never written holds, and at decode step 0 its tag, 0, is this step's)
+          const bool ok = i < G && (cur >> 32) == ep && (uint32_t)cur != 0u;
+          if (ok) key[j] = (uint32_t)cur;
+          valid += __popcll(__ballot(ok));
+        }
+      }
+      uint32_t prefix = 0u;
+      int kr = a.top_k;
+      for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t want = prefix | (1u << bit), hmask = ~((1u << bit) - 1u);
+        int c1 = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (j < nj) c1 += __popcll(__ballot((key[j] & hmask) == want));
+        if (c1 >= kr) prefix = want;
+        else kr -= c1;
+      }
+      if (lane == 0) LBc[m] = valid >= a.top_k ? key2f(prefix) : -INFINITY;
+    }
+  }
+  if (!TOPK && tid < M * 8) {  // (also without the wait: the other shards' maxima so far cut the recompute,
     const int m = tid >> 3;  //  one row 75 -> 68 us, profiles/r6am_ab_shardread_1.txt)
     const unsigned long long cur = __hip_atomic_load(a.lbg + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     float v = (cur >> 32) == ep ? key2f((uint32_t)cur) : -INFINITY;
@@ -560,6 +627,22 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
                                       crow, a.freq_penalty, a.eos_mask[m]);
             if (a.check && !(v <= a.ub[(size_t)m * a.ldu + n]) && v == v)
               __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (TOPK) {
+              // (top-k needs both sides: a score below its lower bound could make T too high)
+              if (a.check && !(v >= a.lbo[(size_t)m * a.ldu + n]) && v == v)
+                __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              // (one atomic per appended candidate: a few hundred a row and step.  Sharing one
+              // add among the 16 lanes of a row — a ballot and a shuffle per row of every unit's
+              // epilogue — measured slower on the step: DESIGN.md 3.6)
+              if (v >= LBc[m]) {
+                const int i = atomicAdd(a.cand_cnt + m, 1);
+                if (i < a.ldc) {  // (never false: every column is appended at most once, ldc >= V)
+                  a.cand_val[(size_t)m * a.ldc + i] = v;
+                  a.cand_idx[(size_t)m * a.ldc + i] = n;
+                }
+              }
+              continue;
+            }
             if (v > bv[mb][r] || (v == bv[mb][r] && n < bi[mb][r])) { bv[mb][r] = v; bi[mb][r] = n; }
           }
         }
@@ -586,7 +669,7 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
       chain(wa, tl[f]);
     }
   }
-  if (wave == kScrWaves - 1) {
+  if (!TOPK && wave == kScrWaves - 1) {
 #pragma unroll
     for (int mb = 0; mb < MTB; ++mb)
 #pragma unroll
@@ -643,6 +726,10 @@ bool head_screen_supported(int M, int K, int V) {
 }
 bool head_screen_prequant(int M) { return M > 16; }
 int head_screen_waves() { return kScrWaves; }
+bool head_screen_topk_supported(int M, int K, int V, int top_k, int grid) {
+  return head_screen_supported(M, K, V) && M <= (K == 2048 ? 16 : 8) && top_k >= 1 && top_k <= HEAD_SCREEN_MAX_TOP_K &&
+         top_k <= grid && grid <= 512;
+}
 
 void launch_head_quant(const bf16_t* w, int V, int K, int ur, int8_t* q, float* cst, hipStream_t s) {
   if (dry_record("head_quant_kernel")) return;
@@ -660,19 +747,32 @@ void launch_head_screen(const HeadScreenArgs& a, int grid, hipStream_t s) {
   if (!head_screen_supported(a.M, a.K, a.V) || a.ur != grid * kScrWaves || (a.V / 16) > kScrMaxUPW * a.ur ||
       a.hKT != a.K / 32 || grid > LOGITS_MAX_PARTS || (pre && (a.K != 2048 || a.normw)))
     throw std::runtime_error("head screen: unsupported shape");
+  const bool topk = a.top_k > 0;
+  if (topk && !head_screen_topk_supported(a.M, a.K, a.V, a.top_k, grid))
+    throw std::runtime_error("head screen: unsupported top-k shape");
   const int mt = scr_mt(a.M), rpw = (a.M + kScrWaves - 1) / kScrWaves;
   const int rp = pre ? 1 : (rpw <= 1 ? 1 : (rpw <= 2 ? 2 : 4));
   if (dry_record("head_screen_kernel<" + std::to_string(mt) + ", " + std::to_string(a.K / 64) + ", " +
-                 std::to_string(rp) + ", " + (pre ? "true" : "false") + ">"))
+                 std::to_string(rp) + ", " + (pre ? "true" : "false") + (topk ? ", true" : "") + ">"))
     return;
+  if (topk && (!a.slots || !a.cand_val || !a.cand_idx || !a.cand_cnt || a.ldc < a.V || (a.check && !a.lbo)))
+    throw std::runtime_error("head screen: missing top-k workspace");
   if (!a.epoch || !a.lbg || !a.arrive || (a.check && !(a.ub && a.err)) || (pre && !(a.xq && a.xstat)))
     throw std::runtime_error("head screen: missing workspace");
   const size_t lds = scr_lds(a.M, a.K);
   HeadScreenArgs b = a;
   if (grid % 8) b.spins = 0;  // (the wait's 8 arrival shards need equal shares of the grid)
-#define TTS_SCR(MT_, KT8_, RP_, PRE_) \
-  hipLaunchKernelGGL((head_screen_kernel<MT_, KT8_, RP_, PRE_>), dim3(grid), dim3(kScrWaves * 64), lds, s, b)
-  if (a.K == 2048) {
+#define TTS_SCR(...) \
+  hipLaunchKernelGGL((head_screen_kernel<__VA_ARGS__>), dim3(grid), dim3(kScrWaves * 64), lds, s, b)
+  if (topk) {
+    if (a.K == 2048) {
+      if (rp == 1) TTS_SCR(1, 32, 1, false, true);
+      else if (rp == 2) TTS_SCR(1, 32, 2, false, true);
+      else TTS_SCR(2, 32, 4, false, true);
+    } else {
+      if (rp == 1) TTS_SCR(1, 64, 1, false, true); else TTS_SCR(1, 64, 2, false, true);
+    }
+  } else if (a.K == 2048) {
     if (pre) TTS_SCR(4, 32, 1, true);
     else if (rp == 1) TTS_SCR(1, 32, 1, false);
     else if (rp == 2) TTS_SCR(1, 32, 2, false);

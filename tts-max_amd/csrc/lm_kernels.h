@@ -226,8 +226,19 @@ struct HeadScreenArgs {
   int ldu = 0;
   int* err = nullptr;             // check mode: set to 1 when a score exceeds its bound
   int diag = 0;                   // probes only (TTS_HEAD_SCREEN_DIAG): 1 skip the recompute (wrong ids), 2 count flagged units
+  // top-k mode (the sampled step; top_k > 0): candidates of the top-k set instead of the argmax
+  int top_k = 0;
+  unsigned long long* slots = nullptr;  // [M][grid] every workgroup's maximum lower bound: (step << 32) | order key
+  float* cand_val = nullptr;      // [M][ldc] exact scores >= the row's threshold, in arrival order
+  int* cand_idx = nullptr;        // [M][ldc] their ids
+  int* cand_cnt = nullptr;        // [M] entries appended (zero at launch: the list's reader clears it)
+  int ldc = 0;                    // >= V
+  float* lbo = nullptr;           // check mode: [M][ldu] lower bound of every processed score
 };
+constexpr int HEAD_SCREEN_MAX_TOP_K = 64;  // top-k mode: top_k <= this (and <= the screen's grid)
 bool head_screen_supported(int M, int K, int V);
+// the sampled step's form: 1..16 rows at K 2048, 1..8 at K 4096, top_k <= min(64, grid)
+bool head_screen_topk_supported(int M, int K, int V, int top_k, int grid);
 bool head_screen_prequant(int M);  // rows quantised by launch_head_rowquant first (17..32 rows, K 2048)
 int head_screen_waves();
 void launch_head_rowquant(const bf16_t* x, int ldx, int M, int K, int8_t* xq, float* xstat, hipStream_t s);
@@ -313,9 +324,18 @@ struct SampleArgs {
   int* out_part_idx = nullptr;
   float* probs = nullptr;         // optional: final distribution [B][ldl] (kept ids only)
   int* tokens = nullptr;          // optional: chosen token [B]
+  // list form (launch_sample_list): logits = the rows' candidate scores [B][ldl], entry i of row b
+  // standing for id list_idx[b][i]; list_cnt[b] entries (at most V = the lists' capacity); vocab =
+  // the dense row's length (top_k >= vocab: no top-k cut; probs rows are [vocab] wide)
+  const int* list_idx = nullptr;
+  int* list_cnt = nullptr;
+  int list_clear = 0;             // 1: zero list_cnt[b] once read (the screened head appends from zero)
+  int vocab = 0;
 };
 constexpr int SAMPLE_MAX_TOP_K = 1024;
 void launch_sample(const SampleArgs& a, int B, hipStream_t s);
+// the same draw from per-row candidate lists that hold (at least) every entry of the top-k set
+void launch_sample_list(const SampleArgs& a, int B, hipStream_t s);
 
 void launch_bump_epoch(uint32_t* epoch, hipStream_t s);  // *epoch += 1 (a decode step without finalize)
 void launch_finalize_greedy(const float* part_val, const int* part_idx, int part_stride,

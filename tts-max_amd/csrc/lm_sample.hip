@@ -61,18 +61,48 @@ TTS_DEV void bitonic_desc(unsigned long long* a, int n) {
   }
 }
 
-__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
+// LIST: the row is a candidate list (a.logits[b][0 .. cnt), ids a.list_idx[b][..], cnt =
+// a.list_cnt[b]) that holds every entry of the top-k set (the screened sampling head appends it,
+// lm_head_screen.hip) instead of the dense row of a.V processed logits; entry i stands for id
+// list_idx[i], everything else is the dense form's code: the same values sort into the same
+// order, so the draw is the dense row's.
+template <bool LIST>
+TTS_DEV void sample_body(const SampleArgs& a) {
   __shared__ unsigned long long cand[SMP_CMAX];
   __shared__ unsigned hist[256];
   __shared__ int s_cnt;
   __shared__ uint32_t s_thr;
   const int b = blockIdx.x, tid = threadIdx.x;
+  int V = a.V;  // entries of the row
+  if constexpr (LIST) {
+    V = min(a.list_cnt[b], a.V);
+    if (a.list_clear) {  // (the producer appends from zero again next step: read by all, then cleared)
+      __syncthreads();
+      if (tid == 0) a.list_cnt[b] = 0;
+    }
+  }
   if (a.done && a.done[b]) return;
+  if (LIST && V <= 0) {
+    // an empty list (no candidate reached the producer's threshold: scores all NaN, or its
+    // recompute switched off by a timing probe) has nothing to sort or draw: token 0, as
+    // finalize's guard for a row without a pick, and no probs
+    if (tid == 0) {
+      if (a.out_part_idx) {
+        a.out_part_val[(size_t)b * a.part_stride] = 0.f;
+        a.out_part_idx[(size_t)b * a.part_stride] = 0;
+      }
+      if (a.tokens) a.tokens[b] = 0;
+    }
+    return;
+  }
   const float* l = a.logits + (size_t)b * a.ldl;
-  const int V = a.V;
+  const int* lid = LIST ? a.list_idx + (size_t)b * a.ldl : nullptr;
+  auto id_of = [&](int i) { return LIST ? (unsigned)lid[i] : (unsigned)i; };
   const bool scale = a.temperature != 1.0f;
   auto sval = [&](int i) { const float v = l[i]; return scale ? v / a.temperature : v; };
-  const int k = (a.top_k > 0 && a.top_k < V) ? a.top_k : V;
+  // (the k of the dense row the list stands for: a list shorter than k keeps all of its entries)
+  const int k = LIST ? ((a.top_k > 0 && a.top_k < a.vocab) ? min(a.top_k, V) : V)
+                     : ((a.top_k > 0 && a.top_k < V) ? a.top_k : V);
 
   // ---- threshold: k-th largest of the lm_head partial maxima (a lower bound), or exact
   uint32_t thr = 0u;  // keep keys >= thr
@@ -89,7 +119,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     thr = (uint32_t)(cand[k - 1] >> 32);
     __syncthreads();
   } else if (k < V) {
-    exact = true;
+    exact = !LIST || V > SMP_CMAX;  // (a list that fits the LDS is its own candidate set)
   }
 
   for (int attempt = 0; attempt < 2; ++attempt) {
@@ -128,7 +158,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
       const uint32_t key = okey(sval(i));
       if (key >= thr) {
         const int c = atomicAdd(&s_cnt, 1);
-        if (c < SMP_CMAX) cand[c] = ((unsigned long long)key << 32) | (unsigned)i;
+        if (c < SMP_CMAX) cand[c] = ((unsigned long long)key << 32) | id_of(i);
       }
     }
     __syncthreads();
@@ -183,7 +213,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     if (a.probs) {
       for (int i = 0; i < nkeep; ++i) {
         const int id = (int)(uint32_t)cand[i];
-        a.probs[(size_t)b * a.ldl + id] = expf(okey_inv((uint32_t)(cand[i] >> 32)) - mx) / z2;
+        a.probs[(size_t)b * (LIST ? a.vocab : a.ldl) + id] = expf(okey_inv((uint32_t)(cand[i] >> 32)) - mx) / z2;
       }
     }
     if (a.out_part_idx) {
@@ -194,11 +224,24 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
   }
 }
 
+__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) { sample_body<false>(a); }
+__global__ __launch_bounds__(SMP_THREADS) void sample_list_kernel(SampleArgs a) { sample_body<true>(a); }
+
 }  // namespace
 
 void launch_sample(const SampleArgs& a, int B, hipStream_t s) {
   if (dry_record("sample_kernel")) return;
   hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(SMP_THREADS), 0, s, a);
+}
+
+void launch_sample_list(const SampleArgs& a, int B, hipStream_t s) {
+  if (dry_record("sample_list_kernel")) return;
+  if (!a.logits || !a.list_idx || !a.list_cnt || a.vocab < 1 || a.V < 1 || a.V > a.ldl)
+    throw std::runtime_error("list sampler: missing list");
+  SampleArgs b = a;
+  b.part_val = nullptr;  // (the list is the candidate set: no partial maxima to bound it)
+  b.nparts = 0;
+  hipLaunchKernelGGL(sample_list_kernel, dim3(B), dim3(SMP_THREADS), 0, s, b);
 }
 
 }  // namespace tts

@@ -57,8 +57,10 @@ EXPORTED_SYMBOLS = (
     "tts_op_retile",
     "tts_op_wgemm",
     "tts_debug_step_plan",
+    "tts_debug_step_plan_sampled",
     "tts_op_pgemm",
     "tts_op_sample",
+    "tts_op_sample_list",
     "tts_op_rmsnorm",
     "tts_op_gemm_f32",
     "tts_op_attn_prefill",
@@ -189,11 +191,13 @@ def load_library() -> ctypes.CDLL:
         "tts_op_wgemm": (I32, [P, I32, I32, I32, P, I32, P, F32, P, I32, P, I32, P]),
         "tts_op_pgemm": (I32, [P, I32, I32, P, I32, P, I32, P, I32, P]),
         "tts_op_sample": (I32, [P, I32, I32, F32, I32, F32, ctypes.c_uint64, I32, P, I32, P, P, P]),
+        "tts_op_sample_list": (I32, [P, P, P, I32, I32, I32, F32, I32, F32, ctypes.c_uint64, I32, P, P, P]),
         "tts_op_rmsnorm": (I32, [P, P, F32, P, I32, I32, P]),
         "tts_op_gemm_f32": (I32, [P, I32, I32, I32, P, I32, P, P, I32, P, I32, P]),
         "tts_op_attn_prefill": (I32, [P, I32, pi32, pi32, pi32, I32, I32, P, P, I32, P, P, I32, I32, I32, F32, P, P, P]),
         "tts_op_attn_decode": (I32, [P, P, I32, I32, I32, P, P, I32, P, P, I32, P, P, I32, I32, I32, F32, P, P]),
         "tts_debug_step_plan": (I32, [ctypes.POINTER(LmConfig), I32, I32, ctypes.c_char_p, I32]),
+        "tts_debug_step_plan_sampled": (I32, [ctypes.POINTER(LmConfig), I32, I32, I32, ctypes.c_char_p, I32]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("TTS_LIB_PATH") and not hasattr(lib, name):

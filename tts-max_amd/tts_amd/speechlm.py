@@ -81,13 +81,18 @@ def lm_config(arch: configs.LmArch, max_batch: int = 1, max_seq_len: int = 2048)
         max_seq_len=max_seq_len)
 
 
-def step_plan(arch: configs.LmArch, rows: int, num_cu: int = 256) -> list[str]:
+def step_plan(arch: configs.LmArch, rows: int, num_cu: int = 256, top_k: int | None = None) -> list[str]:
     """The kernels one decode step over `rows` rows launches (tts_debug_step_plan: the
-    engine's step code in dry-run mode; no GPU needed): unique, in first-seen order."""
+    engine's step code in dry-run mode; no GPU needed): unique, in first-seen order.
+    top_k: the plan of a sampled step with that top_k (tts_debug_step_plan_sampled) instead of
+    the greedy step's."""
     lib = _lib.load_library()
     cfg = lm_config(arch, max_batch=max(rows, 1), max_seq_len=2048)
     buf = ctypes.create_string_buffer(1 << 16)
-    _lib.check(lib.tts_debug_step_plan(ctypes.byref(cfg), rows, num_cu, buf, len(buf)))
+    if top_k is None:
+        _lib.check(lib.tts_debug_step_plan(ctypes.byref(cfg), rows, num_cu, buf, len(buf)))
+    else:
+        _lib.check(lib.tts_debug_step_plan_sampled(ctypes.byref(cfg), rows, num_cu, top_k, buf, len(buf)))
     return [ln for ln in buf.value.decode().splitlines() if ln]
 
 
@@ -373,7 +378,10 @@ class MI355XSpeechLM:
         ms, b = ctypes.c_float(), ctypes.c_double()
         # qkv_attn: QKV with the decode attention fused in (the one-row step's form);
         # qkv_attn_oproj: the same launch also carrying o_proj (the default 1..16-row step)
-        sel = {"qkv_attn": 6, "qkv_attn_oproj": 7, "head_screened": 8, "head_screen": 9}.get(which)
+        # sample_screened / sample_full: the sampled step's head (T 0.8, top_k 50) through the
+        # int8 screen + list sampler / the full lm_head with its logits store + dense sampler
+        sel = {"qkv_attn": 6, "qkv_attn_oproj": 7, "head_screened": 8, "head_screen": 9,
+               "sample_screened": 10, "sample_full": 11}.get(which)
         sel = self.KERNELS.index(which) if sel is None else sel
         _lib.check(self._lib.tts_lm_bench_kernel(self._h, sel, rows, ctx, iters,
                                                  ctypes.byref(ms), ctypes.byref(b)))
