@@ -374,7 +374,7 @@ tts_status tts_op_wgemm(const void* x, int32_t M, int32_t K, int32_t ldx, const 
     a.out = (bf16_t*)out; a.ldo = ldo; a.resid = (bf16_t*)resid;
     // RMSNorm in the GEMM's prologue where the rows fit it (LDS rows, K <= 4096, the LDS-DMA
     // pieces of 512 columns); otherwise a standalone pass first — the same canonical sum order
-    // (chunk_sumsq), so the same bits either way, as the engine does (lm_engine.cpp gemm)
+    // (chunk_sumsq), so the same bits either way, as the engine does (lm_step.cpp Ctx::gemm)
     bf16_t* xn = nullptr;
     if (normw && !(p.a_lds && !p.sliced && K <= 4096 && K % 512 == 0)) {
       HIP_CHECK(hipMallocAsync((void**)&xn, (size_t)M * K * 2, st));
@@ -404,7 +404,7 @@ tts_status tts_op_pgemm(const void* x, int32_t M, int32_t K, const void* w_tiled
     a.w = (const bf16_t*)w_tiled; a.N = N;
     a.out = (bf16_t*)out; a.ldo = ldo; a.resid = (bf16_t*)resid;
     // the engine's scratch for the one-chunk-per-workgroup form (prompts of <= 256 rows,
-    // lm_engine.cpp kPgemmSplitRows): a stream-ordered allocation of this call's size
+    // lm_load.cpp kPgemmSplitRows): a stream-ordered allocation of this call's size
     hipStream_t s = (hipStream_t)stream;
     if (M <= 256) {
       a.part_bytes = pgemm_part_bytes(M, N, K);

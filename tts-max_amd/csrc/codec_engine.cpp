@@ -340,8 +340,7 @@ void gemm_p(const uint16_t* Ap, long long ap_plane, int M, int K, int lda, const
 // TTS_CODEC_BX3=0 (plain fp32 MFMA for every contraction, a debugging switch) turns the
 // split-bf16 x3p path off as well
 bool use_x3p() {
-  static const bool v = !(getenv("TTS_CODEC_X3P") && !atoi(getenv("TTS_CODEC_X3P"))) &&
-                        !(getenv("TTS_CODEC_BX3") && !atoi(getenv("TTS_CODEC_BX3")));
+  static const bool v = env_on("TTS_CODEC_X3P") && env_on("TTS_CODEC_BX3");
   return v;
 }
 
@@ -573,8 +572,7 @@ void codec_decode(Engine* e, const int32_t* codes, const int32_t* lens, int B, f
   float* wav_dev = wav_is_device ? wav : cd.wav.as<float>();
   // passes of at most kPassCodes codes (the workspace grows with a pass: ~90 KB per code
   // at 24 kHz); one utterance longer than that is a pass of its own
-  static const long long kPassCodes =
-      getenv("TTS_CODEC_PASS_CODES") ? atoll(getenv("TTS_CODEC_PASS_CODES")) : 32768;
+  static const long long kPassCodes = env_ll("TTS_CODEC_PASS_CODES", 32768);
   size_t off_codes = 0, off_wav = 0;
   for (int b0 = 0; b0 < B;) {
     int b1 = b0;

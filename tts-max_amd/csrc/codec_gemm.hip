@@ -26,6 +26,7 @@
 #include <stdexcept>
 
 #include "codec_kernels.h"
+#include "env.h"
 #include "hip_common.h"
 
 namespace tts {
@@ -387,10 +388,10 @@ static void launch_x3p(const GemmF32Args& g, hipStream_t s) {
   // wave tiles (a step is long enough to cover the DMA's latency); the two-stage schedule on
   // the small tiles, whose steps are not (one 650-code utterance 4.8 -> 5.3 ms with the first,
   // profiles/r5h_ab_codec_ilv.txt).  TTS_CODEC_X3P_ILV=0 / 1 forces one (A/B)
-  static const int ilv_env = getenv("TTS_CODEC_X3P_ILV") ? atoi(getenv("TTS_CODEC_X3P_ILV")) : -1;
+  static const int ilv_env = env_int("TTS_CODEC_X3P_ILV", -1);
   const bool ilv = NS >= 3 || (ilv_env >= 0 ? ilv_env != 0 : (TM / WM == 64 && TN / WN == 64));
   // TTS_CODEC_X3P_PP=1: the out-of-phase DMA split (PP, above) on the 8-wave tile (experiment)
-  static const bool pp = getenv("TTS_CODEC_X3P_PP") && atoi(getenv("TTS_CODEC_X3P_PP"));
+  static const bool pp = env_set("TTS_CODEC_X3P_PP");
   if (ilv && pp && NS == 2 && WM * WN == 8)
     hipLaunchKernelGGL((gemm_x3p_kernel<TM, TN, WM, WN, true, NS, WM * WN == 8>), dim3(tiles), dim3(64 * WM * WN), lds, s, g);
   else if (ilv) hipLaunchKernelGGL((gemm_x3p_kernel<TM, TN, WM, WN, true, NS>), dim3(tiles), dim3(64 * WM * WN), lds, s, g);
@@ -398,7 +399,7 @@ static void launch_x3p(const GemmF32Args& g, hipStream_t s) {
 }
 
 static bool small4() {
-  static const bool v = getenv("TTS_CODEC_X3P_SMALL4") && atoi(getenv("TTS_CODEC_X3P_SMALL4"));
+  static const bool v = env_set("TTS_CODEC_X3P_SMALL4");
   return v;
 }
 
@@ -415,7 +416,7 @@ void launch_gemm_x3p(const GemmF32Args& g, hipStream_t s) {
   // same bits; a lone utterance's tile choices swept in profiles/r5w_ab_codec1_tile.txt, and
   // 64x64 from half a round, r5z2_ab_codec1_heur.txt, measured the same).  TTS_CODEC_X3P_TILE
   // forces one (0..5).
-  static const int forced = getenv("TTS_CODEC_X3P_TILE") ? atoi(getenv("TTS_CODEC_X3P_TILE")) : -1;
+  static const int forced = env_int("TTS_CODEC_X3P_TILE", -1);
   auto tiles = [&](int tm, int tn) { return ((g.M + tm - 1) / tm) * ((g.N + tn - 1) / tn); };
   int c = forced;
   if (c < 0)

@@ -14,6 +14,7 @@
 #include <stdexcept>
 
 #include "codec_kernels.h"
+#include "env.h"
 #include "hip_common.h"
 
 namespace tts {
@@ -420,7 +421,7 @@ void launch_gemm_f32(const GemmF32Args& g_in, hipStream_t s) {
   g.ksplit = 1;
   g.kchunk = g.K;
   // TTS_CODEC_BX3=0: plain fp32 MFMA for every contraction
-  static const bool bx3 = !(getenv("TTS_CODEC_BX3") && !atoi(getenv("TTS_CODEC_BX3")));
+  static const bool bx3 = env_on("TTS_CODEC_BX3");
   const int big = ((g.M + 127) / 128) * ((g.N + 127) / 128);
   if (bx3 && g.K % 32 == 0 && g.lda % 4 == 0) {
     const dim3 g128(big), g64(((g.M + 63) / 64) * ((g.N + 63) / 64));
@@ -428,7 +429,7 @@ void launch_gemm_f32(const GemmF32Args& g_in, hipStream_t s) {
     // workgroup per CU: fewer operand bytes per MAC, and with 256 columns each A element is
     // split for twice the outputs) where those tiles still make >= 2 rounds of the CUs (the
     // ragged batch's big GEMMs).  (256x256 on 16 waves spills: 4 waves per SIMD leave 128 VGPRs)
-    static const int big_tiles = getenv("TTS_CODEC_TILE") ? atoi(getenv("TTS_CODEC_TILE")) : 1;
+    static const int big_tiles = env_int("TTS_CODEC_TILE", 1);
     const int t21 = ((g.M + 255) / 256) * ((g.N + 127) / 128);
     const int t12 = ((g.M + 127) / 128) * ((g.N + 255) / 256);
     if (g.Bp && g.Ap && big_tiles == 1 && t21 >= 2 * 256)
@@ -918,7 +919,7 @@ void launch_codec_attention(const float* qkv, const CodecSeg* seg, const int2* q
   // libm expf by default: the base-2 v_exp_f32 form measured neutral here (32 x 650 codes 62.0 ms
   // either way, profiles/r4e_ab_codec_expf.txt: the softmax is not what bounds this kernel), so
   // the reference's exp stays.  TTS_CODEC_EXPF=0: v_exp_f32
-  static const int expf_mode = getenv("TTS_CODEC_EXPF") ? atoi(getenv("TTS_CODEC_EXPF")) : 1;
+  static const int expf_mode = env_int("TTS_CODEC_EXPF", 1);
   hipLaunchKernelGGL(codec_attn_kernel<4>, grid, dim3(256), attn_lds(4), s, qkv, seg, qblk, heads,
                      (const float2*)rope_cs, out, expf_mode, outp, plane);
 }

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/tts_mi355x.h"
+#include "env.h"
 #include "lm_kernels.h"
 
 namespace tts {
@@ -80,10 +81,38 @@ struct LmModel {
   int qkv_n() const { return (cfg.num_heads + 2 * cfg.num_kv_heads) * cfg.head_dim; }
 };
 
+// What the captured decode step bakes in as kernel arguments: a generation whose key differs
+// needs a recapture.  (The sampling keys are per-row device values, LmWork::row_seed: a new
+// seed needs none.)  temp / top_k / top_p count only for a sampled step (-1 when greedy).
+struct StepKey {
+  int batch = -1;
+  float pen = -1.f;
+  int eos = -2, min_new = -1;
+  int sample = -1, top_k = -1;
+  float temp = -1.f, top_p = -1.f;
+  float freq = 0.f;
+  StepKey() = default;
+  StepKey(int B, const tts_gen_params& p)
+      : batch(B), pen(p.repetition_penalty), eos(p.eos_token_id), min_new(p.min_new_tokens),
+        sample(p.do_sample), top_k(p.do_sample ? p.top_k : -1), temp(p.do_sample ? p.temperature : -1.f),
+        top_p(p.do_sample ? p.top_p : -1.f), freq(p.frequency_penalty) {}
+  bool operator==(const StepKey& o) const {
+    return batch == o.batch && pen == o.pen && eos == o.eos && min_new == o.min_new && sample == o.sample &&
+           top_k == o.top_k && temp == o.temp && top_p == o.top_p && freq == o.freq;
+  }
+};
+
+// LmWork::ferr: ints the kernels raise and read_device_flags (lm_generate.cpp) reports
+enum {
+  FERR_GRANULE_TIMEOUT = 0,  // fused QKV+attention: a granule wait timed out
+  FERR_SCREEN_CHECK = 1,     // screened lm_head, check mode: a score outside its bound (the launch's `err`)
+  FERR_SCREEN_DIAG = 3,      // TTS_HEAD_SCREEN_DIAG=2: units recomputed (the launch counts at err[2])
+  FERR_SLOTS = 4
+};
+
 struct LmWork {
   int cap_rows = 0;    // activation rows (prefill rows and decode batch)
   int cap_batch = 0;
-  int cap_seq = 0;
   DevBuf kv;           // per layer: K [slots][KVH][kv_stride][D], V^T [slots][KVH][D][kv_stride]
   int kv_stride = 0;   // positions per (slot, kv head) strip: max_seq_len rounded up to 64
   DevBuf x, xn, qkv, attn_out, act, q_rot, last_x;  // activations
@@ -99,7 +128,6 @@ struct LmWork {
   DevBuf ppart;                                     // prefill GEMM fp32 partials [chunks][rows][N] (lm_pgemm.hip)
   DevBuf slogits;                                   // sampling: processed fp32 logits [B][V]
   DevBuf counts;                                    // vLLM frequency penalty: new-token counts [B][V] u16
-  DevBuf logits;                                    // scoring output (bf16)
   DevBuf row_slot, row_pos, row_idx;                // prefill row descriptors
   DevBuf st_int;                                    // step-state ints
   DevBuf row_seed;                                  // [B] u64 sampling key of each row (graph-invariant)
@@ -107,13 +135,7 @@ struct LmWork {
   DevBuf out_ids;                                   // [B][max_new]
   int out_cap = 0;
   hipGraphExec_t graph = nullptr;
-  int graph_batch = -1;  // the captured step bakes in B, penalty, eos and min_new
-  float graph_pen = -1.f;
-  int graph_eos = -2, graph_min_new = -1;
-  // sampling parameters baked into the captured step (kernel arguments)
-  int graph_sample = -1, graph_top_k = -1;
-  float graph_temp = -1.f, graph_top_p = -1.f;
-  float graph_freq = 0.f;
+  StepKey step_key;  // what `graph` was captured with
   int* h_active = nullptr;  // pinned host copy of n_active (ring of 2)
 };
 
@@ -176,7 +198,6 @@ std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k
 
 // upload a named tensor to device memory as bf16 (convert from f32 if needed)
 void upload_bf16(const tts_tensor_desc& d, bf16_t* dst, hipStream_t s, DevBuf& staging);
-void upload_f32(const tts_tensor_desc& d, float* dst, hipStream_t s, DevBuf& staging);
 int64_t numel(const tts_tensor_desc& d);
 
 void codec_load(Engine* e, const tts_codec_config* cfg, const tts_tensor_desc* t, int n);

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <stdexcept>
 
+#include "env.h"
 #include "lm_gemm_kernel.h"
 
 namespace tts {
@@ -105,7 +106,7 @@ StreamPlan stream_plan(int N, int K, int ng, int num_cu) {
   p.grid = std::min(grid, cap);
   // between one and two rounds of units per CU, a full grid leaves half the workgroups with
   // one round more than the rest (TTS-1-Max qkv: 384 units on 256 CUs): balance the rounds
-  static const bool balance = !(getenv("TTS_BALANCE") && !atoi(getenv("TTS_BALANCE")));
+  static const bool balance = env_on("TTS_BALANCE");
   if (balance && fgrid <= 0 && grid > num_cu && grid < 2 * num_cu) p.grid = (grid + 1) / 2;
   // K chunks of 2048 columns (64 k-tiles) where the shape divides them: at batch 17..32 one
   // chunk of A (32 x 2048 bf16 = 128 KiB) fits LDS where the whole K (8192) does not
@@ -146,7 +147,7 @@ WgemmPlan plan_wgemm(int M, int N, int K, int epi, int num_cu) {
   if (K % 512 != 0) p.a_lds = false;
   // experiment hook: TTS_HEAD_GRID=<workgroups> for the lm_head launch (units are walked
   // grid-stride, so any grid covers them; at most LOGITS_MAX_PARTS argmax partials)
-  static const int head_grid = getenv("TTS_HEAD_GRID") ? atoi(getenv("TTS_HEAD_GRID")) : 0;
+  static const int head_grid = env_int("TTS_HEAD_GRID", 0);
   if (epi == EPI_LOGITS && head_grid > 0) p.grid = std::min(head_grid, LOGITS_MAX_PARTS);
   // Up to 16 rows, a residual projection whose rows do not fit the LDS prologue and whose
   // K-sliced form would run the grid in more than two rounds (TTS-1-Max down, K 14336: 7
@@ -154,7 +155,7 @@ WgemmPlan plan_wgemm(int M, int N, int K, int epi, int num_cu) {
   // ring) instead: at 8 rows 39 -> 23 us.  (TTS-1 down at 16 rows, 4 chunks x 128: the
   // sliced form is faster, 14.5 vs 15.5 us; at 17..32 rows the ring drops to one stage and
   // loses.)  Unsliced also keeps these rows' sums in the batch-1 order.  TTS_AGR=0: off.
-  static const bool agr_on = !(getenv("TTS_AGR") && !atoi(getenv("TTS_AGR")));
+  static const bool agr_on = env_on("TTS_AGR");
   if (agr_on && M <= 16 && epi == EPI_RESID && !p.a_lds && p.sp.kc > 1 && p.grid * p.sp.kc > 2 * num_cu)
     return p;  // a_lds = false, unsliced
   // (17..32 rows with A fragments from L2 beside the weight tiles instead of the LDS rows,
@@ -162,13 +163,13 @@ WgemmPlan plan_wgemm(int M, int N, int K, int epi, int num_cu) {
   // removed in round 6: profiles/r4c_ab_agr32.txt, r2_ab_norm32.txt)
   // Residual projections with K chunks run K-sliced from 8 rows on even where the rows fit the
   // LDS prologue (TTS-1's down at 8..9 rows), so the per-row combine normalises each row once
-  // for the next QKV launch (lm_engine.cpp, TTS_NORM_ONCE): 8 rows 753 -> 748 us a step; at 2 and 4
+  // for the next QKV launch (lm_step.cpp, TTS_NORM_ONCE): 8 rows 753 -> 748 us a step; at 2 and 4
   // rows it loses (671 -> 692, 706 -> 713 us; profiles/r6f_ab_slice_*.txt).  Only matrices of
   // four or more K chunks (a down projection): a 2-chunk o_proj (TTS-1-Max, K 4096) must keep the
   // unsliced sum order of the o_proj that rides the 2..16-row QKV launch, so the separate and
   // fused forms give the same bits.  TTS_SLICE_RESID_ROWS=<n> moves the threshold (0: only where
   // the rows do not fit)
-  static const int slice_rows = getenv("TTS_SLICE_RESID_ROWS") ? atoi(getenv("TTS_SLICE_RESID_ROWS")) : 8;
+  static const int slice_rows = env_int("TTS_SLICE_RESID_ROWS", 8);
   const bool force_slice = slice_rows > 0 && M >= slice_rows && epi == EPI_RESID && p.sp.kc >= 4;
   if ((!p.a_lds || force_slice) && p.sp.kc > 1 && (epi == EPI_STORE || epi == EPI_RESID) &&
       wgemm_lds_bytes(w, ks, ng, M, K / p.sp.kc, true) <= kLdsBudget) {
@@ -179,13 +180,13 @@ WgemmPlan plan_wgemm(int M, int N, int K, int epi, int num_cu) {
     // so the launch grid is free).  TTS-1 down at 32 rows: 128 x 4 workgroups in two rounds,
     // each staging 128 KiB of A for 64 KiB of weights -> 64 x 4: 19.5 -> 15.6 us, step
     // 1,228 -> 1,179 us, same ids (profiles/r2_ab_sliced_grid.txt).  TTS_SLICED_GRID=0: off.
-    static const bool one_round = !(getenv("TTS_SLICED_GRID") && !atoi(getenv("TTS_SLICED_GRID")));
+    static const bool one_round = env_on("TTS_SLICED_GRID");
     if (one_round) p.grid = std::max(1, std::min(p.grid, (num_cu + p.sp.kc - 1) / p.sp.kc));
   }
   // A matrix with at most half a unit per CU (TTS-1 o_proj and down at 1..16 rows: 128 units)
   // streams each unit as two 8-column halves on twice the workgroups: every CU pulls half
   // the bytes.  TTS_CSPLIT=0: off; =2: also at 17..64 rows.
-  static const int csplit_mode = getenv("TTS_CSPLIT") ? atoi(getenv("TTS_CSPLIT")) : 1;
+  static const int csplit_mode = env_int("TTS_CSPLIT", 1);
   const int units = (N / 16) / ng;
   const int upw = w / ks;
   if (csplit_mode > 0 && (M <= 16 || csplit_mode == 2) && !p.sliced && p.a_lds &&
@@ -240,7 +241,7 @@ void launch_wgemm(const WgemmArgs& a_in, const WgemmPlan& p_in, int epi, bool no
   a.csplit = p.csplit;
   if (a.csplit == 2 && epi != EPI_STORE && epi != EPI_RESID)
     throw std::runtime_error("wgemm: column split only for plain store / residual launches");
-  static const int diag = getenv("TTS_WGEMM_DIAG") ? atoi(getenv("TTS_WGEMM_DIAG")) : 0;
+  static const int diag = env_int("TTS_WGEMM_DIAG", 0);
   a.diag = diag;
   if (p.sliced) {
     // one K chunk per workgroup row of the grid: fp32 partials, then the epilogue in a

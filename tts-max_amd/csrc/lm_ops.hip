@@ -1,6 +1,7 @@
 // lm_ops.hip — small SpeechLM kernels: standalone RMSNorm (prefill chunks), token
 // embedding gather, row gather, greedy finalize (argmax reduce + per-sequence bookkeeping),
 // and the deterministic synthetic-weight generator shared with tts_amd/synth.py.
+#include "env.h"
 #include "hip_common.h"
 #include "lm_kernels.h"
 #include "lm_finalize.h"
@@ -340,7 +341,7 @@ __global__ __launch_bounds__(256) void splitk_combine_norm_fixed_kernel(
 
 void launch_splitk_combine_norm(const float* part, int kc, int M, int N, int ldp, bf16_t* resid, int ldo,
                                 const bf16_t* normw, float eps, bf16_t* xn, int ldn, hipStream_t s) {
-  static const bool fixed = !(getenv("TTS_COMBINE_FIXED") && !atoi(getenv("TTS_COMBINE_FIXED")));
+  static const bool fixed = env_on("TTS_COMBINE_FIXED");
   if (dry_record("splitk_combine_norm")) return;
   if (fixed && N == 2048 && kc == 4)
     hipLaunchKernelGGL((splitk_combine_norm_fixed_kernel<4, 1>), dim3(M), dim3(256), 0, s, part, M, ldp, resid, ldo,

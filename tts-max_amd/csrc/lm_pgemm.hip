@@ -26,6 +26,7 @@
 // block of output tiles, so the weight tiles and A rows they share are fetched into that
 // XCD's L2 once.  The weight loads use the default cache policy (they are re-read by every
 // m-block: MI355X_MICROARCH.md nt-weights, "never on slices that every CU re-reads").
+#include "env.h"
 #include "hip_common.h"
 #include "lm_kernels.h"
 
@@ -328,8 +329,8 @@ bool launch_pgemm(const PgemmArgs& a_in, int epi, int num_cu, hipStream_t s) {
   // workgroup (2.31 -> 2.79 ms), =1 also for the SwiGLU gate/up, whose 512 tiles already cover
   // the CUs (2.19 -> 2.31 ms: the partials cost more than the shorter chains save;
   // profiles/r6i_prefill_ab.txt)
-  static const bool xcd_env = !getenv("TTS_PGEMM_XCD") || atoi(getenv("TTS_PGEMM_XCD"));
-  static const int split_env = getenv("TTS_PGEMM_SPLIT") ? atoi(getenv("TTS_PGEMM_SPLIT")) : 2;
+  static const bool xcd_env = env_on("TTS_PGEMM_XCD");
+  static const int split_env = env_int("TTS_PGEMM_SPLIT", 2);
   a.xcd_order = xcd_env;
   const StreamPlan sp = stream_plan(a.N, a.K, epi == EPI_SWIGLU ? 2 : 1, num_cu);
   a.ng = sp.ng; a.ksplit = sp.ksplit; a.ku = sp.ku; a.ur = sp.ur(); a.kc = sp.kc;
