@@ -55,8 +55,9 @@ for k in ("qkv", "o_proj", "gate_up", "down", "attention", "qkv_attn", "qkv_attn
     if k in ("qkv_attn", "qkv_attn_oproj"):
         # grid order: projection | attention | o_proj workgroups
         na = rows * arch.num_kv_heads
-        # (the one-row o_proj workgroups write no stamps; the 2..16-row ones do, last in the grid)
-        no = arch.hidden_size // 16 if (k == "qkv_attn_oproj" and rows > 1) else 0
+        # (the o_proj workgroups come last in the grid; one row: "row 0 granules" = wave 0's
+        # granules seen, "all rows" = its MFMAs done)
+        no = arch.hidden_size // 16 if k == "qkv_attn_oproj" else 0
         nq = len(us) - na - no  # projection workgroups
         proj, cons = us[:nq], us[nq:nq + na]
         if no:

@@ -29,6 +29,8 @@
 // The maximum is taken over all waves first (LDS), then p, l and P.V; the waves' partial O
 // and l are summed in wave order through LDS.
 #pragma once
+#include <type_traits>
+
 #include "hip_common.h"
 
 namespace tts {
@@ -98,57 +100,53 @@ TTS_DEV void dec_load_v(const bf16_t* vtc, int S, int base, int lane,
   }
 }
 
-// The new position (ctx - 1) is not in the cache yet: its roped k / its v (LDS, bf16) replace
-// the stale row / column elements in the fragments; V elements past ctx are zeroed (their p is
-// 0, and 0 * NaN from never-written memory would poison the sum).  Branch-free: the LDS values
-// are read unconditionally and merged with bit masks (a select whose operand is a load is
-// otherwise turned into a branch around the load, and every such branch also drains vmcnt).
-TTS_DEV uint32_t bits_sel(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }
-// Only the wave whose positions [base, base + PW) reach the new position pn = ctx - 1 has
-// anything to patch or to mask: below pn dec_patch_k's mask is 0, dec_patch_v's keep is all
-// ones and its put 0, and every position is < ctx.  One wave per pass is such a tail wave (the
-// waves past ctx do not run), so the others skip the patches and the < ctx select — the same
-// bits.  The branches are register-critical (the kernels sit at 116..128 VGPRs): the condition
-// goes through readfirstlane, each branch stands between scheduling barriers, the V patch comes
-// after the scores (kf is dead by then; both patches in one branch spilled 14..30 VGPRs at
-// head dim 128), and dec_patch_k reads the new k one k-step at a time (all at once: 4 spills).
+// The new position pn = ctx - 1 is not in the cache yet.  Its score comes from an MFMA chain of
+// its own over the roped new k (dec_scores); its v (LDS, bf16) replaces the stale column
+// elements in the V^T fragments, and the V elements past ctx are zeroed (their p is 0, and
+// 0 * NaN from never-written memory would poison the sum): V's share is inside the P.V sums
+// and cannot be taken apart without another summation order.  The LDS values are read
+// unconditionally and merged with bit masks (a select whose operand is a load is otherwise
+// turned into a branch around the load, and every such branch also drains vmcnt).
+// Only the wave whose positions [base, base + PW) reach pn has anything to patch or to mask:
+// below pn dec_patch_v's keep is all ones and its put 0, and every position is < ctx.  One wave
+// per pass is such a tail wave (the waves past ctx do not run), so the others skip the patch,
+// the extra chain and the < ctx select — the same bits.  The branches are register-critical
+// (the kernels sit at 110..126 VGPRs): the condition goes through readfirstlane, each branch
+// stands between scheduling barriers, and the V patch comes after the scores (kf is dead by then).
 template <int PW>
 TTS_DEV bool dec_tail(int base, int ctx) { return __builtin_amdgcn_readfirstlane(base + PW > ctx - 1) != 0; }
-template <int D, int PW>
-TTS_DEV void dec_patch_k(int base, int ctx, int lane, const bf16_t* knew,
-                         u32x4_t (&kf)[DecShape<D, PW>::MT][DecShape<D, PW>::KS]) {
-  using C = DecShape<D, PW>;
-  const int c = lane & 15, g = lane >> 4, pn = ctx - 1;
-  uint32_t m[C::MT];
-#pragma unroll
-  for (int mt = 0; mt < C::MT; ++mt) m[mt] = dec_pos(base, mt, c) == pn ? 0xffffffffu : 0u;
-#pragma unroll
-  for (int ks = 0; ks < C::KS; ++ks) {
-    const u32x4_t kn = *(const u32x4_t*)(knew + 32 * ks + 8 * g);
-#pragma unroll
-    for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) kf[mt][ks][q] = bits_sel(m[mt], kn[q], kf[mt][ks][q]);
-  }
-}
 template <int D, int PW>
 TTS_DEV void dec_patch_v(int base, int ctx, int lane, const bf16_t* vnew,
                          u32x4_t (&vf)[DecShape<D, PW>::PS][DecShape<D, PW>::DT]) {
   using C = DecShape<D, PW>;
-  const int c = lane & 15, g = lane >> 4, pn = ctx - 1;
+  const int c = lane & 15, g = lane >> 4;
+  // Called by the tail wave only (base <= pn < base + PW), so the place of pn = ctx - 1 in the
+  // fragments is wave-uniform: k-step rel >> 5, lane group (rel >> 3) & 3, word (rel >> 1) & 3,
+  // half rel & 1.  The word masks of that lane group are scalars, a lane takes them, all ones
+  // (its group lies below pn's) or zero (beyond); a k-step wholly below pn is left alone and one
+  // wholly beyond is zeroed — the masks the per-element compares gave, an eighth of the VALU.
+  const int rel = __builtin_amdgcn_readfirstlane(ctx - 1 - base);
   uint32_t vn[C::DT];
 #pragma unroll
   for (int dt = 0; dt < C::DT; ++dt) vn[dt] = vnew[16 * dt + c];
 #pragma unroll
   for (int ps = 0; ps < C::PS; ++ps) {
-    const int p0 = base + 32 * ps + 8 * g;
+    const int rp = rel - 32 * ps;
+    if (C::PS > 1 && rp >= 32) continue;
+    if (C::PS > 1 && rp < 0) {
+#pragma unroll
+      for (int dt = 0; dt < C::DT; ++dt) vf[ps][dt] = u32x4_t{0u, 0u, 0u, 0u};
+      continue;
+    }
+    const int gs = rp >> 3, es = (rp >> 1) & 3;
+    const uint32_t hk = (rp & 1) ? 0x0000ffffu : 0u, hp = (rp & 1) ? 0xffff0000u : 0x0000ffffu;
     // per 32-bit word e2 (elements 2 e2, 2 e2 + 1): keep mask and new-value mask
     uint32_t keep[4], put[4];
 #pragma unroll
     for (int e2 = 0; e2 < 4; ++e2) {
-      const int pl = p0 + 2 * e2, ph = pl + 1;
-      keep[e2] = (pl < pn ? 0x0000ffffu : 0u) | (ph < pn ? 0xffff0000u : 0u);
-      put[e2] = (pl == pn ? 0x0000ffffu : 0u) | (ph == pn ? 0xffff0000u : 0u);
+      const uint32_t ke = e2 < es ? 0xffffffffu : (e2 == es ? hk : 0u), pe = e2 == es ? hp : 0u;
+      keep[e2] = g < gs ? 0xffffffffu : (g == gs ? ke : 0u);
+      put[e2] = g == gs ? pe : 0u;
     }
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt) {
@@ -169,9 +167,19 @@ TTS_DEV bf16x8_t dec_qfrag(const bf16_t* qs, int lane, int ks) {
 
 // S^T of one pass (scaled, positions >= ctx at -inf).  tail (wave-uniform, dec_tail): the
 // wave's positions reach ctx - 1 or beyond; in every other wave the < ctx select is the identity.
+// The tail wave takes the score of the new position pn = ctx - 1 from one extra MFMA chain over
+// the same k-steps with the roped new k (knew, LDS) in every A row, beside the chains over the
+// unpatched fragments (an output element of an MFMA is the same chain of products whatever the
+// other rows hold: the bits a patched K row gave), and selects it into pn's accumulator slot; the
+// stale row's own score (never-written memory: possibly NaN) is discarded there like the
+// positions beyond.  Element r of m-tile 2 ps + h is position base + 32 ps + 8 g + 4 h + r
+// (dec_pos): below pn where 8 g + 4 h + r < rel - 32 ps, rel = pn - base wave-uniform — a k-step
+// wholly below pn is left alone, one wholly beyond is -inf, and in the one between a lane
+// compares the elements' constants against d = rel - 32 ps - 8 g.
 template <int D, int PW>
 TTS_DEV void dec_scores(const u32x4_t (&kf)[DecShape<D, PW>::MT][DecShape<D, PW>::KS], const bf16_t* qs,
-                        int base, int ctx, float scale, int lane, bool tail, f32x4_t (&s)[DecShape<D, PW>::MT]) {
+                        const bf16_t* knew, int base, int ctx, float scale, int lane, bool tail,
+                        f32x4_t (&s)[DecShape<D, PW>::MT]) {
   using C = DecShape<D, PW>;
   const int g = lane >> 4;
 #pragma unroll
@@ -189,10 +197,34 @@ TTS_DEV void dec_scores(const u32x4_t (&kf)[DecShape<D, PW>::MT][DecShape<D, PW>
     for (int r = 0; r < 4; ++r) s[mt][r] *= scale;
   __builtin_amdgcn_sched_barrier(0);
   if (tail) {
+    // (behind the chains over kf, whose registers are free by now: ahead of them the extra
+    // chain's operands cost 2 VGPRs more than the parent's K patch)
+    f32x4_t sn = {0.f, 0.f, 0.f, 0.f};  // every row: the new position's scores of heads lane & 3
 #pragma unroll
-    for (int mt = 0; mt < C::MT; ++mt)
+    for (int ks = 0; ks < C::KS; ++ks) {
+      const bf16x8_t kn = __builtin_bit_cast(bf16x8_t, *(const u32x4_t*)(knew + 32 * ks + 8 * g));
+      sn = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kn, dec_qfrag<D>(qs, lane, ks), sn, 0, 0, 0);
+    }
+    const float snew = sn[0] * scale;
+    const int rel = __builtin_amdgcn_readfirstlane(ctx - 1 - base);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) s[mt][r] = (dec_pos(base, mt, 4 * g + r) < ctx) ? s[mt][r] : -INFINITY;
+    for (int ps = 0; ps < C::PS; ++ps) {
+      const int rp = rel - 32 * ps;
+      if (C::PS > 1 && rp >= 32) continue;
+      if (C::PS > 1 && rp < 0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) s[2 * ps + h] = f32x4_t{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        continue;
+      }
+      const int d = rp - 8 * g;  // pn's element in this lane: < 0 = its group lies beyond pn, > 7 = below
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float beyond = 4 * h + r == d ? snew : -INFINITY;
+          s[2 * ps + h][r] = 4 * h + r < d ? s[2 * ps + h][r] : beyond;
+        }
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -229,6 +261,27 @@ TTS_DEV void dec_pv(float M, float& lsum, f32x4_t (&s)[DecShape<D, PW>::MT],
 template <int D, int NW>
 constexpr int dec_red_floats() { return NW * DEC_G * 2 + NW * DEC_G * D; }
 
+// The exchanges between the waves (maximum, l, partial O) run over the first NL slots only:
+// NL = the waves that hold positions, rounded up to a quarter of NW (dec_ladder: a wave-uniform
+// choice among four compile-time forms, so that every read of an exchange is still in flight
+// before its first use; a run-time bound would make it a dependent loop).  The skipped slots
+// would hold -inf (maximum) and +0.0 (l, O: sums that start at +0.0 and are therefore never
+// -0.0), the identities of the two operations, and the order of the terms left is unchanged:
+// the same bits.  The waves past NL do not store their slots.
+template <int NW, int PW>
+TTS_DEV int dec_ladder(int ctx) {
+  static_assert(NW % 4 == 0, "four ladder steps");
+  const int na = (ctx + PW - 1) / PW;  // waves holding positions in pass 0
+  return __builtin_amdgcn_readfirstlane(min(NW, (na + NW / 4 - 1) / (NW / 4) * (NW / 4)));
+}
+template <int NW, class F>
+TTS_DEV void dec_ladder_call(int nl, F f) {
+  if (nl <= NW / 4) f(std::integral_constant<int, NW / 4>{});
+  else if (nl <= NW / 2) f(std::integral_constant<int, NW / 2>{});
+  else if (nl <= 3 * NW / 4) f(std::integral_constant<int, 3 * NW / 4>{});
+  else f(std::integral_constant<int, NW>{});
+}
+
 // The whole attention of one (row, kv head) by the NW waves of the workgroup (called by every
 // thread; contains barriers).  kf0 / vf0: this wave's pass-0 fragments, already issued (the
 // callers load them before anything else).  qs: roped q [4][D] bf16 (LDS, visible); knew /
@@ -251,6 +304,7 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   float* lred = red + NW * DEC_G;    // [NW][4]
   float* ored = lred + NW * DEC_G;   // [NW][4][D]
   const int base0 = wave * PW;
+  const int nl = dec_ladder<NW, PW>(ctx);  // slots the exchanges run over (>= the waves holding positions)
 
   // phase 1: the context maximum per head (pass 0 from the prefetched fragments, its scores
   // kept; later passes (contexts beyond NW * PW positions) reload K only)
@@ -258,13 +312,7 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   float mx = -INFINITY;
   const bool tail0 = dec_tail<PW>(base0, ctx);
   if (base0 < ctx) {
-    __builtin_amdgcn_sched_barrier(0);
-    if (tail0) {
-      dec_patch_k<D, PW>(base0, ctx, lane, knew, kf0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    dec_scores<D, PW>(kf0, qs, base0, ctx, scale, lane, tail0, s0);
+    dec_scores<D, PW>(kf0, qs, knew, base0, ctx, scale, lane, tail0, s0);
 #pragma unroll
     for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
@@ -276,14 +324,8 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
     u32x4_t kf[C::MT][C::KS];
     dec_load_k<D, PW, O32>(kc, base, ctx, lane, kf);
     const bool tail = dec_tail<PW>(base, ctx);
-    __builtin_amdgcn_sched_barrier(0);
-    if (tail) {
-      dec_patch_k<D, PW>(base, ctx, lane, knew, kf);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
     f32x4_t s[C::MT];
-    dec_scores<D, PW>(kf, qs, base, ctx, scale, lane, tail, s);
+    dec_scores<D, PW>(kf, qs, knew, base, ctx, scale, lane, tail, s);
 #pragma unroll
     for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
@@ -291,7 +333,7 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   }
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  if (lane < DEC_G) mred[wave * DEC_G + lane] = mx;
+  if (lane < DEC_G && wave < nl) mred[wave * DEC_G + lane] = mx;
   // (the tail wave's V patch behind its maximum: the other waves wait for that at the barrier)
   __builtin_amdgcn_sched_barrier(0);
   if (base0 < ctx && tail0) {
@@ -301,9 +343,13 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   __builtin_amdgcn_sched_barrier(0);
   bar();
   TTS_STAMP(stp, 5);
-  float M = -INFINITY;
+  float M = -INFINITY;  // (read by the waves that hold positions only: base0 >= ctx has no pass)
+  if (base0 < ctx) {
+    dec_ladder_call<NW>(nl, [&](auto NL) {
 #pragma unroll
-  for (int w = 0; w < NW; ++w) M = fmaxf(M, mred[w * DEC_G + (c & 3)]);
+      for (int w = 0; w < decltype(NL)::value; ++w) M = fmaxf(M, mred[w * DEC_G + (c & 3)]);
+    });
+  }
 
   // phase 2: p, l and P.V
   float lsum = 0.f;
@@ -318,14 +364,8 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
     dec_load_v<D, PW, O32>(vtc, S, base, lane, vf);
     dec_load_k<D, PW, O32>(kc, base, ctx, lane, kf);
     const bool tail = dec_tail<PW>(base, ctx);
-    __builtin_amdgcn_sched_barrier(0);
-    if (tail) {
-      dec_patch_k<D, PW>(base, ctx, lane, knew, kf);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
     f32x4_t s[C::MT];
-    dec_scores<D, PW>(kf, qs, base, ctx, scale, lane, tail, s);
+    dec_scores<D, PW>(kf, qs, knew, base, ctx, scale, lane, tail, s);
     if (tail) {
       dec_patch_v<D, PW>(base, ctx, lane, vnew, vf);
       __builtin_amdgcn_sched_barrier(0);
@@ -336,7 +376,7 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   lsum += __shfl_xor(lsum, 16, 64);
   lsum += __shfl_xor(lsum, 32, 64);
   // lane (c < 4, g) holds O^T[dim 16 dt + 4 g + r][head c]
-  if (c < DEC_G) {
+  if (c < DEC_G && wave < nl) {
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt)
       *(float4*)(ored + (wave * DEC_G + c) * D + 16 * dt + 4 * g) = make_float4(o[dt][0], o[dt][1], o[dt][2], o[dt][3]);
@@ -348,16 +388,19 @@ TTS_DEV void dec_attend_w(const bf16_t* kc, const bf16_t* vtc, int S, int ctx, f
   bf16_t gob = 0;  // (granule output: this thread's element, i == tid: one iteration)
   for (int i = tid; i < DEC_G * D; i += NW * 64) {
     const int h = i / D, d = i - h * D;
-    float v[NW];  // each group of reads in flight before its sums (wave order: deterministic)
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v[w] = lred[w * DEC_G + h];
     float O = 0.f, L = 0.f;
+    dec_ladder_call<NW>(nl, [&](auto NL) {
+      constexpr int N = decltype(NL)::value;
+      float v[N];  // each group of reads in flight before its sums (wave order: deterministic)
 #pragma unroll
-    for (int w = 0; w < NW; ++w) L += v[w];
+      for (int w = 0; w < N; ++w) v[w] = lred[w * DEC_G + h];
 #pragma unroll
-    for (int w = 0; w < NW; ++w) v[w] = ored[(w * DEC_G + h) * D + d];
+      for (int w = 0; w < N; ++w) L += v[w];
 #pragma unroll
-    for (int w = 0; w < NW; ++w) O += v[w];
+      for (int w = 0; w < N; ++w) v[w] = ored[(w * DEC_G + h) * D + d];
+#pragma unroll
+      for (int w = 0; w < N; ++w) O += v[w];
+    });
     const bf16_t ob = f2bf(O / L);
     out[h * D + d] = ob;
     if (gout) gob = ob;

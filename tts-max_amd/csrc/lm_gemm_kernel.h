@@ -149,6 +149,9 @@ TTS_DEV bf16x8_t as_bf16x8(u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); 
 // (one per lane: the attention row of kv group kpart / 2), stages them in LDS and multiplies.
 template <int KU, int KSPLIT, int R>
 TTS_DEV void fused_oproj(const WgemmArgs& a, bf16_t* xs, float* red, int wave, int lane, uint32_t tag, int u) {
+  // (stamps, diagnostic build: entry / wave 0's granules seen / its MFMAs done / combined and stored)
+  unsigned long long* stp = a.stamps ? a.stamps + (size_t)blockIdx.x * 32 : nullptr;
+  TTS_STAMP(stp, 0);
   const int kpart = wave % KSPLIT;
   const int nr = min(a.fo_ur, a.fo_units);
   u32x4_t wr[R][KU];
@@ -167,6 +170,7 @@ TTS_DEV void fused_oproj(const WgemmArgs& a, bf16_t* xs, float* red, int wave, i
   }, a.fattn_err, a.fattn_spins, lane == 0);
   // this wave's 128 attention values into its own K range of the LDS row (read back by this
   // wave only: LDS operations of one wave complete in order)
+  TTS_STAMP(stp, 1);
   *(uint32_t*)(xs + kpart * 128 + 2 * lane) = (uint32_t)v;
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
@@ -179,23 +183,23 @@ TTS_DEV void fused_oproj(const WgemmArgs& a, bf16_t* xs, float* red, int wave, i
       const u32x4_t av = *(const u32x4_t*)(xs + k);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(av), as_bf16x8(wr[st][kk]), acc, 0, 0, 0);
     }
-  // split-K combine (as the GEMM kernel's: 16-B partials, p ascending), residual epilogue
-  if (kpart > 0) *(f32x4_t*)(red + ((size_t)(kpart - 1) * 64 + lane) * 4) = acc;
+  TTS_STAMP(stp, 2);
+  // split-K combine (as the GEMM kernel's: p ascending), residual epilogue.  One row: only row 0
+  // of the accumulator tile is real (lanes 0..15, element 0), so a k-part's partial is those 16
+  // floats — one 4-B LDS access per k-part instead of a 16-B one of all 64 lanes, and all 15
+  // reads in flight before the first add
+  if (kpart > 0 && lane < 16) red[(kpart - 1) * 16 + lane] = acc[0];
   lds_barrier();
   if (kpart == 0) {
-    constexpr int HB = 8;  // reads in flight per batch (register budget of the 16-wave launch)
+    float pv[KSPLIT > 1 ? KSPLIT - 1 : 1];
 #pragma unroll
-    for (int p0 = 1; p0 < KSPLIT; p0 += HB) {
-      f32x4_t pv[HB];
+    for (int p = 1; p < KSPLIT; ++p) pv[p - 1] = red[(p - 1) * 16 + (lane & 15)];
+    float r0 = acc[0];
 #pragma unroll
-      for (int j = 0; j < HB; ++j)
-        if (p0 + j < KSPLIT) pv[j] = *(const f32x4_t*)(red + ((size_t)(p0 + j - 1) * 64 + lane) * 4);
-#pragma unroll
-      for (int j = 0; j < HB; ++j)
-        if (p0 + j < KSPLIT) acc += pv[j];
-    }
-    if (lane < 16) a.fo_resid[u * 16 + lane] = f2bf(bf2f(rr) + rbf(acc[0]));
+    for (int p = 1; p < KSPLIT; ++p) r0 += pv[p - 1];
+    if (lane < 16) a.fo_resid[u * 16 + lane] = f2bf(bf2f(rr) + rbf(r0));
   }
+  TTS_STAMP(stp, 3);
 }
 
 // The same for the 2..16-row QKV launch (FROWS): o_proj unit u on its own workgroup.
