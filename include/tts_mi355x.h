@@ -172,6 +172,25 @@ tts_status tts_slots_add(tts_engine* e, int32_t slot, const int32_t* prompt_ids,
  * derives a distinct key per admitted request from the batch seed (p->seed). */
 tts_status tts_slots_add_seeded(tts_engine* e, int32_t slot, const int32_t* prompt_ids, int32_t prompt_len,
                                 int32_t max_new_tokens, uint64_t seed);
+/* Per-request settings (vLLM builds one SamplingParams per call and decodes them in one running
+ * batch).  As tts_slots_open, but every admitted request may carry its own settings; `defaults`
+ * serve requests that give none.  The captured step then reads temperature, top_k, top_p, the
+ * penalties, min_new_tokens and the stop id of every row from a device table, so a request with
+ * new settings costs no recapture.  Rows still never mix: each sequence's tokens equal those of a
+ * tts_slots_open batch (or a batch-1 tts_generate) run with that request's settings and key.
+ * Greedy and sampled requests share the batch.  Up to 16 rows (8 at hidden size 4096) with every
+ * resident top_k <= 64 the step picks through the screened lm_head; a request with a larger top_k
+ * moves the batch to the full lm_head (one recapture, until the batch is reopened), and batches of
+ * 17..32 rows always take the full lm_head. */
+tts_status tts_slots_open_per_request(tts_engine* e, const tts_gen_params* defaults, int32_t n_slots, void* stream);
+/* p NULL: the batch defaults.  seed NULL: a key derived from the batch seed as tts_slots_add does
+ * (p->seed and p->max_length are ignored).  Only valid on a per-request batch: on a batch opened
+ * with tts_slots_open a non-NULL p returns TTS_E_STATE.  p is checked as tts_slots_open checks
+ * its settings, plus temperature >= 0 and repetition_penalty finite and > 0; a bad request returns
+ * TTS_E_INVALID, leaves the slot free and the other rows untouched.  tts_slots_add and
+ * tts_slots_add_seeded work on both kinds of batch (the defaults). */
+tts_status tts_slots_add_params(tts_engine* e, int32_t slot, const int32_t* prompt_ids, int32_t prompt_len,
+                                int32_t max_new_tokens, const tts_gen_params* p, const uint64_t* seed);
 tts_status tts_slots_step(tts_engine* e, int32_t n_steps, int32_t* n_active);
 tts_status tts_slots_read(tts_engine* e, int32_t slot, int32_t* out_ids, int32_t capacity, int32_t* n_out,
                           int32_t* finished);

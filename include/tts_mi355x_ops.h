@@ -65,6 +65,20 @@ tts_status tts_op_sample_list(const float* scores, const int32_t* ids, const int
                               int32_t cap, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
                               int32_t step, float* probs, int32_t* tokens, void* stream);
 
+/* The per-row samplers of the per-request slot batch, alone: row b samples with temperature[b],
+ * top_k[b] (1..1024), top_p[b] and the key row_seed[b] (the draw of tts_op_sample with that seed on
+ * the row alone: u = splitmix64(row_seed[b], 0, step)) when sample[b] != 0; sample[b] == 0 is a
+ * greedy row: the argmax by float comparison, lowest id on ties (+0.0 and -0.0 tie), untouched by
+ * the temperature, and no probs.  The five settings arrays are device arrays of B entries (the
+ * kernel reads them; nothing checks their values).  ids NULL: dense rows scores [B][V] (cap
+ * unused); part_max / part_idx [B][nparts] are optional, as in tts_op_sample (a greedy row then
+ * reduces the partials instead of the row).  ids set: candidate lists as tts_op_sample_list
+ * (counts required, only read; part_* unused).  probs optional. */
+tts_status tts_op_sample_rows(const float* scores, const int32_t* ids, const int32_t* counts, int32_t B, int32_t cap,
+                              int32_t V, const float* temperature, const int32_t* top_k, const float* top_p,
+                              const int32_t* sample, const uint64_t* row_seed, int32_t step, const float* part_max,
+                              const int32_t* part_idx, int32_t nparts, float* probs, int32_t* tokens, void* stream);
+
 /* Diagnostics, no GPU needed: the kernels one decode step over `rows` rows of a model of
  * config `cfg` would launch on a GPU of `num_cu` CUs — the engine's own step code run with
  * its launchers in a dry-run mode (nothing allocated or launched).  Writes the unique launches
@@ -77,6 +91,13 @@ tts_status tts_debug_step_plan(const tts_lm_config* cfg, int32_t rows, int32_t n
  * else the full lm_head with its logits store + sample_kernel. */
 tts_status tts_debug_step_plan_sampled(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t top_k,
                                        char* out, int32_t cap);
+
+/* ... of the per-request batch's step (tts_slots_open_per_request) whose largest admitted top_k is
+ * max_top_k: the screen's per-row top-k variant (head_screen_kernel<MT, KT8, rows per wave + 8, false, true>) +
+ * sample_list_rows_kernel where the rows and max_top_k fit the screen, else the full lm_head with
+ * the per-row epilogue (wgemm_kernel<..., 4, ...>) + sample_rows_kernel. */
+tts_status tts_debug_step_plan_rows(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t max_top_k,
+                                    char* out, int32_t cap);
 
 /* LlamaRMSNorm over rows of x (bf16). */
 tts_status tts_op_rmsnorm(const void* x, const void* w, float eps, void* y, int32_t M, int32_t K,

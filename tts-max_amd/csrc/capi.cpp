@@ -141,6 +141,25 @@ tts_status tts_slots_open(tts_engine* e, const tts_gen_params* p, int32_t n_slot
   });
 }
 
+tts_status tts_slots_open_per_request(tts_engine* e, const tts_gen_params* defaults, int32_t n_slots, void* stream) {
+  return guarded([&] {
+    TTS_REQUIRE(e && defaults, "null argument");
+    Engine* E = reinterpret_cast<Engine*>(e);
+    HIP_CHECK(hipSetDevice(E->device));
+    lm_slots_open(E, defaults, n_slots, pick_stream(E, stream), true);
+  });
+}
+
+tts_status tts_slots_add_params(tts_engine* e, int32_t slot, const int32_t* prompt_ids, int32_t prompt_len,
+                                int32_t max_new_tokens, const tts_gen_params* p, const uint64_t* seed) {
+  return guarded([&] {
+    TTS_REQUIRE(e && prompt_ids, "null argument");
+    Engine* E = reinterpret_cast<Engine*>(e);
+    HIP_CHECK(hipSetDevice(E->device));
+    lm_slots_add(E, slot, prompt_ids, prompt_len, max_new_tokens, seed, p);
+  });
+}
+
 tts_status tts_slots_add(tts_engine* e, int32_t slot, const int32_t* prompt_ids, int32_t prompt_len,
                          int32_t max_new_tokens) {
   return guarded([&] {
@@ -256,6 +275,17 @@ tts_status tts_debug_step_plan_sampled(const tts_lm_config* cfg, int32_t rows, i
     TTS_REQUIRE(cfg && out && cap > 0, "null argument");
     TTS_REQUIRE(top_k >= 1 && top_k <= SAMPLE_MAX_TOP_K, "top_k in [1, 1024]");
     const std::string p = lm_step_plan(*cfg, rows, num_cu, top_k);
+    TTS_REQUIRE((int64_t)p.size() < cap, "output buffer too small");
+    memcpy(out, p.c_str(), p.size() + 1);
+  });
+}
+
+tts_status tts_debug_step_plan_rows(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t max_top_k,
+                                    char* out, int32_t cap) {
+  return guarded([&] {
+    TTS_REQUIRE(cfg && out && cap > 0, "null argument");
+    TTS_REQUIRE(max_top_k >= 1 && max_top_k <= SAMPLE_MAX_TOP_K, "max_top_k in [1, 1024]");
+    const std::string p = lm_step_plan(*cfg, rows, num_cu, max_top_k, true);
     TTS_REQUIRE((int64_t)p.size() < cap, "output buffer too small");
     memcpy(out, p.c_str(), p.size() + 1);
   });
@@ -446,6 +476,35 @@ tts_status tts_op_sample_list(const float* scores, const int32_t* ids, const int
     a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.step0 = step;
     a.probs = probs; a.tokens = tokens;
     launch_sample_list(a, B, (hipStream_t)stream);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+tts_status tts_op_sample_rows(const float* scores, const int32_t* ids, const int32_t* counts, int32_t B, int32_t cap,
+                              int32_t V, const float* temperature, const int32_t* top_k, const float* top_p,
+                              const int32_t* sample, const uint64_t* row_seed, int32_t step, const float* part_max,
+                              const int32_t* part_idx, int32_t nparts, float* probs, int32_t* tokens, void* stream) {
+  return guarded([&] {
+    TTS_REQUIRE(scores && tokens && B >= 1 && V >= 1, "bad arguments");
+    TTS_REQUIRE(temperature && top_k && top_p && sample && row_seed, "missing per-row settings");
+    TTS_REQUIRE((ids == nullptr) == (counts == nullptr), "a list needs ids and counts");
+    SampleArgs a;
+    a.logits = scores;
+    a.row_temp = temperature; a.row_top_k = top_k; a.row_top_p = top_p; a.row_sample = sample; a.row_stride = 1;
+    a.row_seed = (const unsigned long long*)row_seed; a.step0 = step;
+    a.probs = probs; a.tokens = tokens;
+    if (ids) {
+      TTS_REQUIRE(cap >= 1, "bad arguments");
+      a.list_idx = ids; a.list_cnt = const_cast<int32_t*>(counts);  // (list_clear 0: only read)
+      a.ldl = cap; a.V = cap; a.vocab = V;
+      launch_sample_list_rows(a, B, (hipStream_t)stream);
+    } else {
+      a.ldl = V; a.V = V;
+      const bool parts = part_max != nullptr && nparts > 0;
+      a.part_val = parts ? part_max : nullptr; a.part_idx = parts ? part_idx : nullptr;
+      a.nparts = parts ? nparts : 0; a.part_stride = nparts;
+      launch_sample_rows(a, B, (hipStream_t)stream);
+    }
     HIP_CHECK(hipGetLastError());
   });
 }

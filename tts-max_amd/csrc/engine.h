@@ -84,6 +84,10 @@ struct LmModel {
 // What the captured decode step bakes in as kernel arguments: a generation whose key differs
 // needs a recapture.  (The sampling keys are per-row device values, LmWork::row_seed: a new
 // seed needs none.)  temp / top_k / top_p count only for a sampled step (-1 when greedy).
+// per_row (the per-request slot batch): the settings are per-row device values too
+// (LmWork::row_par) and the other settings fields stay neutral, so admitting a request with new
+// settings needs no recapture; dense = the step takes the full lm_head + the dense sampler instead
+// of the screen's per-row top-k form (a resident request's top_k is above what the screen covers).
 struct StepKey {
   int batch = -1;
   float pen = -1.f;
@@ -91,14 +95,21 @@ struct StepKey {
   int sample = -1, top_k = -1;
   float temp = -1.f, top_p = -1.f;
   float freq = 0.f;
+  int per_row = 0, dense = 0;
   StepKey() = default;
+  static StepKey rows(int B, bool dense) {
+    StepKey k;
+    k.batch = B; k.per_row = 1; k.dense = dense ? 1 : 0;
+    return k;
+  }
   StepKey(int B, const tts_gen_params& p)
       : batch(B), pen(p.repetition_penalty), eos(p.eos_token_id), min_new(p.min_new_tokens),
         sample(p.do_sample), top_k(p.do_sample ? p.top_k : -1), temp(p.do_sample ? p.temperature : -1.f),
         top_p(p.do_sample ? p.top_p : -1.f), freq(p.frequency_penalty) {}
   bool operator==(const StepKey& o) const {
     return batch == o.batch && pen == o.pen && eos == o.eos && min_new == o.min_new && sample == o.sample &&
-           top_k == o.top_k && temp == o.temp && top_p == o.top_p && freq == o.freq;
+           top_k == o.top_k && temp == o.temp && top_p == o.top_p && freq == o.freq && per_row == o.per_row &&
+           dense == o.dense;
   }
 };
 
@@ -131,6 +142,7 @@ struct LmWork {
   DevBuf row_slot, row_pos, row_idx;                // prefill row descriptors
   DevBuf st_int;                                    // step-state ints
   DevBuf row_seed;                                  // [B] u64 sampling key of each row (graph-invariant)
+  DevBuf row_par;                                   // [cap_batch] RowParams: the per-request slot batch's settings table
   DevBuf seen;                                      // [B][V/32]
   DevBuf out_ids;                                   // [B][max_new]
   int out_cap = 0;
@@ -167,6 +179,10 @@ struct Engine {
     int S = 0;
     tts_gen_params gp{};
     unsigned long long next_req = 0;  // default per-request sampling keys
+    // per-request batch (tts_slots_open_per_request): every row's settings in LmWork::row_par (gp =
+    // the defaults); dense: a request above the screen's top_k bound was admitted (until reopened)
+    bool per_row = false, dense = false;
+    int max_top_k = 1;  // the largest top_k admitted so far (the screen's host check)
     std::vector<int> busy;  // 1 while a sequence owns the slot (until released)
     hipStream_t s = nullptr;
   } slots;
@@ -183,8 +199,10 @@ void lm_gen_begin(Engine* e, const tts_gen_params* p, const int32_t* ids, const 
                   hipStream_t s);
 int lm_gen_continue(Engine* e, int n_steps);
 void lm_gen_read(Engine* e, int32_t* out_ids, int out_stride, int32_t* out_lens);
-void lm_slots_open(Engine* e, const tts_gen_params* p, int S, hipStream_t s);
-void lm_slots_add(Engine* e, int slot, const int32_t* prompt, int len, int max_new, const uint64_t* seed);
+void lm_slots_open(Engine* e, const tts_gen_params* p, int S, hipStream_t s, bool per_request = false);
+// rp: the request's own settings (a per-request batch only), or nullptr: the batch's
+void lm_slots_add(Engine* e, int slot, const int32_t* prompt, int len, int max_new, const uint64_t* seed,
+                  const tts_gen_params* rp = nullptr);
 int lm_slots_step(Engine* e, int n_steps);
 void lm_slots_read(Engine* e, int slot, int32_t* out_ids, int cap, int32_t* n_out, int32_t* finished);
 void lm_slots_release(Engine* e, int slot);
@@ -194,7 +212,8 @@ void lm_score_decode(Engine* e, const int32_t* ids, const int32_t* lens, int B, 
                      const int32_t* gidx, int k, float* out, hipStream_t s);
 void lm_bench_kernel(Engine* e, int which, int rows, int ctx, int iters, float* avg_ms,
                      double* bytes);
-std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k = 0);  // top_k > 0: a sampled step
+// top_k > 0: a sampled step; per_row: the per-request batch's step (top_k = its largest admitted top_k)
+std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k = 0, bool per_row = false);
 
 // upload a named tensor to device memory as bf16 (convert from f32 if needed)
 void upload_bf16(const tts_tensor_desc& d, bf16_t* dst, hipStream_t s, DevBuf& staging);

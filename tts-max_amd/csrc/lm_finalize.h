@@ -57,8 +57,11 @@ TTS_DEV void finalize_row(const float* pv, const int* pi, int nparts, const Step
     if (st.counts) st.counts[(size_t)b * st.seen_stride * 32 + tok] += 1;
     st.tokens[b] = tok;
     st.pos[b] = pos0 + 1;
-    const bool stop = (tok == st.eos_id) || (g + 1 >= lim);
-    st.eos_mask[b] = (g + 1 < st.min_new) ? st.eos_id : -1;
+    // (per-request slot batch: the row's own stop id and minimum length)
+    const int eos_id = st.par ? st.par[b].eos_id : st.eos_id;
+    const int min_new = st.par ? st.par[b].min_new : st.min_new;
+    const bool stop = (tok == eos_id) || (g + 1 >= lim);
+    st.eos_mask[b] = (g + 1 < min_new) ? eos_id : -1;
     if (stop) {
       st.done[b] = 1;
       atomicSub(st.n_active, 1);

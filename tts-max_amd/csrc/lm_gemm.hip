@@ -148,7 +148,7 @@ WgemmPlan plan_wgemm(int M, int N, int K, int epi, int num_cu) {
   // experiment hook: TTS_HEAD_GRID=<workgroups> for the lm_head launch (units are walked
   // grid-stride, so any grid covers them; at most LOGITS_MAX_PARTS argmax partials)
   static const int head_grid = env_int("TTS_HEAD_GRID", 0);
-  if (epi == EPI_LOGITS && head_grid > 0) p.grid = std::min(head_grid, LOGITS_MAX_PARTS);
+  if ((epi == EPI_LOGITS || epi == EPI_LOGITS_ROWS) && head_grid > 0) p.grid = std::min(head_grid, LOGITS_MAX_PARTS);
   // Up to 16 rows, a residual projection whose rows do not fit the LDS prologue and whose
   // K-sliced form would run the grid in more than two rounds (TTS-1-Max down, K 14336: 7
   // chunks x 256 workgroups) streams its A fragments from L2 beside the weights (A_GLOBAL
@@ -267,6 +267,7 @@ void launch_wgemm(const WgemmArgs& a_in, const WgemmPlan& p_in, int epi, bool no
     case EPI_RESID: launch_wgemm_resid(a, p, norm, s); break;
     case EPI_SWIGLU: launch_wgemm_swiglu(a, p, norm, s); break;
     case EPI_LOGITS: launch_wgemm_logits(a, p, norm, s); break;
+    case EPI_LOGITS_ROWS: launch_wgemm_logits_rows(a, p, norm, s); break;
   }
 }
 

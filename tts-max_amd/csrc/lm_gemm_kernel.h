@@ -329,6 +329,7 @@ template <int WAVES, int KU, int MT_MAX, int NG, int KSPLIT, int ASRC, bool NORM
 __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NT = WAVES * 64;
+  constexpr bool LOGITS = EPI == EPI_LOGITS || EPI == EPI_LOGITS_ROWS;  // the lm_head epilogue (ROWS: per-row penalties)
   // (one row: the register-staged prologue (EARLY); 2..16 rows (one m-tile): any prologue)
   // (the one-row form carries head dim 64 only, wgemm_fattn_ok: the KU 4 (head dim 128)
   // register-staged instantiation keeps the consumer's registers out)
@@ -478,7 +479,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
       if constexpr (EPI == EPI_RESID) {
         rre[mt][r] = a.resid[(size_t)m * a.ldo + (u_first >> cs2) * 16 + (lane & 15)];
       }
-      if constexpr (EPI == EPI_LOGITS) {
+      if constexpr (LOGITS) {
         eosr[mt][r] = a.eos_mask[m];
         seen_cur[mt][r] = a.seen[(size_t)m * a.seen_stride + (u_first >> 1)];
       }
@@ -712,7 +713,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
     u = ubase + ugrp;
     const bool active = u < units;
     uint32_t seen_nxt[MT_MAX][4];
-    if constexpr (EPI == EPI_LOGITS) {  // next unit's penalty bits, in flight with this unit
+    if constexpr (LOGITS) {  // next unit's penalty bits, in flight with this unit
       const int un = min(u + ustride, units - 1);
 #pragma unroll
       for (int mt = 0; mt < MT_MAX; ++mt)
@@ -862,11 +863,18 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
             const float gt = rbf(acc[0][mt][r]);
             const float up = rbf(acc[NG - 1][mt][r]);
             a.out[(size_t)m * a.ldo + n] = f2bf(rbf(silu_f(gt)) * up);
-          } else if constexpr (EPI == EPI_LOGITS) {
+          } else if constexpr (LOGITS) {
             float v = rbf(acc[0][mt][r]);  // logits are materialised in bf16, then .float()
             const uint32_t bits = seen_cur[mt][r];
-            if ((bits >> (n & 31)) & 1u) v = (v < 0.f) ? v * a.penalty : v / a.penalty;
-            if (a.counts) v -= a.freq_penalty * (float)a.counts[(size_t)m * a.seen_stride * 32 + n];
+            if constexpr (EPI == EPI_LOGITS_ROWS) {
+              // the row's own penalties (one 8-byte load beside the counts'); freq 0 subtracts an exact zero
+              const float2 pf = *(const float2*)(a.row_par + m);
+              if ((bits >> (n & 31)) & 1u) v = (v < 0.f) ? v * pf.x : v / pf.x;
+              v -= pf.y * (float)a.counts[(size_t)m * a.seen_stride * 32 + n];
+            } else {
+              if ((bits >> (n & 31)) & 1u) v = (v < 0.f) ? v * a.penalty : v / a.penalty;
+              if (a.counts) v -= a.freq_penalty * (float)a.counts[(size_t)m * a.seen_stride * 32 + n];
+            }
             if (n == eosr[mt][r]) v = -INFINITY;
             if (a.logits_out) a.logits_out[(size_t)m * a.ldl + n] = v;
             argmax_merge(best_v[mt][r], best_i[mt][r], v, n);
@@ -903,7 +911,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
     }
     if (first) TTS_STAMP(stp, 3);
     first = false;
-    if constexpr (EPI == EPI_LOGITS) {
+    if constexpr (LOGITS) {
 #pragma unroll
       for (int mt = 0; mt < MT_MAX; ++mt)
 #pragma unroll
@@ -916,7 +924,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
     for (int ubase = bx * UPW; ubase < units; ubase += ustride) unit_body(ubase, std::false_type{});
   }
 
-  if constexpr (EPI == EPI_LOGITS) {
+  if constexpr (LOGITS) {
     // lanes sharing (lane >> 4) hold the same rows: butterfly over the 16 columns
 #pragma unroll
     for (int mt = 0; mt < MT_MAX; ++mt)
@@ -1091,5 +1099,6 @@ void launch_wgemm_store(const WgemmArgs& a, const WgemmPlan& p, bool norm, hipSt
 void launch_wgemm_resid(const WgemmArgs& a, const WgemmPlan& p, bool norm, hipStream_t s);
 void launch_wgemm_swiglu(const WgemmArgs& a, const WgemmPlan& p, bool norm, hipStream_t s);
 void launch_wgemm_logits(const WgemmArgs& a, const WgemmPlan& p, bool norm, hipStream_t s);
+void launch_wgemm_logits_rows(const WgemmArgs& a, const WgemmPlan& p, bool norm, hipStream_t s);
 
 }  // namespace tts

@@ -18,9 +18,11 @@ static constexpr int kPollEvery = 8;
 
 // The decode step (all layers + lm_head + pick + finalize over B rows) captured once into a
 // hipGraph, recaptured when what it bakes in (StepKey) changes.
-static void ensure_step_graph(Engine* e, int B, const StepState& st, const tts_gen_params& gp) {
+// per_row: the per-request batch's step (settings in LmWork::row_par; max_top_k / dense choose its form)
+static void ensure_step_graph(Engine* e, int B, const StepState& st, const tts_gen_params& gp, bool per_row = false,
+                              bool dense = false, int max_top_k = 1) {
   LmWork& W = e->w;
-  const StepKey key(B, gp);
+  const StepKey key = per_row ? StepKey::rows(B, dense) : StepKey(B, gp);
   if (W.graph && !(W.step_key == key)) {
     (void)hipGraphExecDestroy(W.graph);
     W.graph = nullptr;
@@ -32,7 +34,8 @@ static void ensure_step_graph(Engine* e, int B, const StepState& st, const tts_g
   HIP_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
   Ctx Y(e, cs);
   Y.layers(B, W.row_slot.as<int>(), st.pos, true);
-  Y.head_and_pick(W.x.as<bf16_t>(), B, st, gp);
+  if (per_row) Y.head_and_pick_rows(W.x.as<bf16_t>(), B, st, dense, max_top_k);
+  else Y.head_and_pick(W.x.as<bf16_t>(), B, st, gp);
   HIP_CHECK(hipStreamEndCapture(cs, &g));
   HIP_CHECK(hipGraphInstantiate(&W.graph, g, nullptr, nullptr, 0));
   HIP_CHECK(hipGraphDestroy(g));
@@ -50,6 +53,23 @@ static void validate_gen_params(const tts_gen_params* p) {
     TTS_REQUIRE(p->top_p > 0.f && p->top_p <= 1.f, "top_p must be in (0, 1]");
   }
   TTS_REQUIRE(std::isfinite(p->frequency_penalty), "frequency_penalty must be finite");
+}
+// ... of a per-request batch (its defaults and every request's own): the penalty divides every
+// row's seen logits, idle rows included
+static void validate_row_params(const tts_gen_params* p) {
+  validate_gen_params(p);
+  TTS_REQUIRE(std::isfinite(p->repetition_penalty) && p->repetition_penalty > 0.f,
+              "repetition_penalty must be finite and > 0");
+  TTS_REQUIRE(std::isfinite(p->temperature) && p->temperature >= 0.f, "temperature must be finite and >= 0");
+}
+// a request's row of the settings table (a greedy row: top_k 1, the screen's k)
+static RowParams row_params(const tts_gen_params& p) {
+  RowParams r;
+  r.penalty = p.repetition_penalty; r.freq_penalty = p.frequency_penalty;
+  r.temperature = p.do_sample ? p.temperature : 1.f; r.top_p = p.do_sample ? p.top_p : 1.f;
+  r.top_k = p.do_sample ? p.top_k : 1; r.eos_id = p.eos_token_id; r.min_new = p.min_new_tokens;
+  r.sample = p.do_sample ? 1 : 0;
+  return r;
 }
 
 void lm_gen_begin(Engine* e, const tts_gen_params* p, const int32_t* ids, const int32_t* lens, int B,
@@ -226,13 +246,15 @@ void lm_generate(Engine* e, const tts_gen_params* p, const int32_t* ids, const i
 static StepState slots_state(Engine* e, hipStream_t s) {
   Engine::Slots& Z = e->slots;
   StepState st = Ctx(e, s).state(Z.S, Z.gp.eos_token_id, Z.gp.min_new_tokens);
-  if (Z.gp.frequency_penalty != 0.f) st.counts = e->w.counts.as<uint16_t>();
+  if (Z.gp.frequency_penalty != 0.f || Z.per_row) st.counts = e->w.counts.as<uint16_t>();
+  if (Z.per_row) st.par = e->w.row_par.as<RowParams>();
   return st;
 }
 
-void lm_slots_open(Engine* e, const tts_gen_params* p, int S, hipStream_t s) {
+void lm_slots_open(Engine* e, const tts_gen_params* p, int S, hipStream_t s, bool per_request) {
   TTS_REQUIRE(e->lm.loaded, "tts_lm_load has not been called");
-  validate_gen_params(p);
+  if (per_request) validate_row_params(p);
+  else validate_gen_params(p);
   TTS_REQUIRE(S >= 1 && S <= e->w.cap_batch, "slot count out of range (max_batch)");
   e->gen.open = false;
   Engine::Slots& Z = e->slots;
@@ -242,7 +264,17 @@ void lm_slots_open(Engine* e, const tts_gen_params* p, int S, hipStream_t s) {
   Z.busy.assign(S, 0);
   Z.next_req = 0;
   Z.s = s;
+  Z.per_row = per_request;
+  Z.max_top_k = p->do_sample ? p->top_k : 1;
   const int V = e->lm.cfg.vocab_size;
+  // (above the screen's top_k bound from the start: the full head)
+  Z.dense = per_request && !Ctx(e, s).rows_screen_ok(S, Z.max_top_k);
+  if (per_request) {  // every row holds valid settings (idle rows are computed too): the defaults
+    const std::vector<RowParams> tab((size_t)S, row_params(*p));
+    HIP_CHECK(hipMemcpyAsync(e->w.row_par.p, tab.data(), tab.size() * sizeof(RowParams), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(e->w.counts.p, 0, (size_t)S * (V / 32 + 1) * 32 * 2, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // (tab is a local buffer)
+  }
   // every row idle: done = 1, n_active = 0, no EOS mask
   std::vector<int> st_host = st_zeros(S);
   for (int b = 0; b < S; ++b) { st_host[st_at(ST_DONE, S, b)] = 1; st_host[st_at(ST_EOS_MASK, S, b)] = -1; }
@@ -250,15 +282,20 @@ void lm_slots_open(Engine* e, const tts_gen_params* p, int S, hipStream_t s) {
   HIP_CHECK(hipMemsetAsync(e->w.seen.p, 0, (size_t)S * (V / 32 + 1) * 4, s));
   Ctx(e, s).upload_identity_slots(S);
   const StepState st = slots_state(e, s);
-  ensure_step_graph(e, S, st, Z.gp);
+  ensure_step_graph(e, S, st, Z.gp, Z.per_row, Z.dense, Z.max_top_k);
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // seed: the request's sampling key (vLLM SamplingParams.seed); nullptr = the batch seed
 // mixed with a request counter, so every request draws its own stream
-void lm_slots_add(Engine* e, int slot, const int32_t* prompt, int len, int max_new, const uint64_t* seed) {
+void lm_slots_add(Engine* e, int slot, const int32_t* prompt, int len, int max_new, const uint64_t* seed,
+                  const tts_gen_params* rp) {
   Engine::Slots& Z = e->slots;
   TTS_REQUIRE(Z.open, "no slot batch open (tts_slots_open)");
+  if (rp && !Z.per_row) throw Error(TTS_E_STATE, "per-request settings need tts_slots_open_per_request");
+  if (rp) validate_row_params(rp);  // (before anything is written: a bad request leaves every row as it was)
+  tts_gen_params gp = rp ? *rp : Z.gp;  // the request's settings (seed and max_length: the batch's)
+  gp.seed = Z.gp.seed; gp.max_length = Z.gp.max_length;
   TTS_REQUIRE(slot >= 0 && slot < Z.S && !Z.busy[slot], "slot out of range or busy");
   TTS_REQUIRE(prompt != nullptr && len >= 1, "empty prompt");
   const tts_lm_config& c = e->lm.cfg;
@@ -282,7 +319,7 @@ void lm_slots_add(Engine* e, int slot, const int32_t* prompt, int len, int max_n
   int row[ST_N_ACTIVE] = {};  // (tokens, gen_count and done start at 0)
   row[ST_POS] = len - 1;
   row[ST_LIMIT] = max_new;
-  row[ST_EOS_MASK] = (Z.gp.min_new_tokens > 0) ? Z.gp.eos_token_id : -1;
+  row[ST_EOS_MASK] = (gp.min_new_tokens > 0) ? gp.eos_token_id : -1;
   for (int k = 0; k < ST_N_ACTIVE; ++k)
     HIP_CHECK(hipMemcpyAsync(e->w.st_int.as<int>() + st_at(k, S, slot), &row[k], 4, hipMemcpyHostToDevice, s));
   // the row's sampling key: the same for its first token (drawn below as a batch of 1) and
@@ -294,12 +331,27 @@ void lm_slots_add(Engine* e, int slot, const int32_t* prompt, int len, int max_n
   HIP_CHECK(hipMemcpyAsync(st.n_active, &act, 4, hipMemcpyHostToDevice, s));
   // ---- prefill the prompt into the slot's KV strip, pick its first token
   X.prefill_group(prompt, &len, 1, slot, 0);
-  X.head_and_pick(e->w.last_x.as<bf16_t>(), 1, step_state_row(st, slot), Z.gp);  // (a batch of 1)
+  if (Z.per_row) {
+    // the row's settings for the captured step; a request above the screen's top_k bound moves the
+    // step to the full head (one recapture; stays until the batch is reopened)
+    const RowParams r = row_params(gp);
+    HIP_CHECK(hipMemcpyAsync(e->w.row_par.as<RowParams>() + slot, &r, sizeof r, hipMemcpyHostToDevice, s));
+    Z.max_top_k = std::max(Z.max_top_k, r.top_k);
+    if (!Z.dense && !X.rows_screen_ok(S, Z.max_top_k)) Z.dense = true;
+    HIP_CHECK(hipStreamSynchronize(s));  // (r is a stack buffer)
+  }
+  // the first token: the uniform kernels over a batch of 1, given the request's settings
+  StepState one = step_state_row(st, slot);
+  one.par = nullptr;
+  one.eos_id = gp.eos_token_id; one.min_new = gp.min_new_tokens;
+  if (Z.per_row && gp.frequency_penalty == 0.f) one.counts = nullptr;  // (as a uniform batch without the penalty)
+  X.head_and_pick(e->w.last_x.as<bf16_t>(), 1, one, gp);
   // the prefill overwrote the decode rows of w.x: re-embed every row's next token
   X.upload_identity_slots(S);
   launch_embed(st.tokens, e->lm.embed_rows.as<bf16_t>(), e->w.x.as<bf16_t>(), S, c.hidden_size, s);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(s));
+  if (Z.per_row) ensure_step_graph(e, S, st, Z.gp, true, Z.dense, Z.max_top_k);  // (recaptured when dense flipped)
   Z.busy[slot] = 1;
 }
 

@@ -252,9 +252,20 @@ TTS_DEV float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k 
 // row's candidate list (capacity V: a column is appended at most once; the count is zeroed by the
 // list's reader, sample_list_kernel).  The list holds the whole top-k set, so the sampler's sort
 // and cut give the dense row's draw.  Workgroups may use different T: each is a valid bound.
-template <int MT, int KT8, int RPW, bool PRE, bool TOPK = false>
+//
+// ROWS (the per-request slot batch, a variant of TOPK): penalty, 1 / penalty, the frequency
+// penalty and top_k are row m's own (a.par[m]) in the bounds, the exact recompute and the
+// k-th-slot select; a greedy row's table entry has top_k 1 (its list then holds the maximum and
+// its ties).  The counts are always read (a row without a frequency penalty subtracts an exact
+// zero).  The flag rides the rows-per-wave argument (RPWF = RPW + kScrRowsFlag), so the uniform
+// instantiations keep their five arguments, their names and their code.
+constexpr int kScrRowsFlag = 8;
+template <int MT, int KT8, int RPWF, bool PRE, bool TOPK = false>
 __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenArgs a) {
+  constexpr int RPW = RPWF & (kScrRowsFlag - 1);
+  constexpr bool ROWS = (RPWF & kScrRowsFlag) != 0;
   static_assert(!(PRE && TOPK), "the top-k mode covers the non-prequantised forms");
+  static_assert(TOPK || !ROWS, "per-row settings: the top-k mode only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int K = KT8 * 64, ldA = K + 16, ldX = K + 8, KU = kScrKU, R = kScrR, S = KT8 / KU, CPL = K / 512;
   constexpr int MMAX = 8 * MT;  // rows of the int8 image (two A rows each)
@@ -304,6 +315,17 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int p = 0; p < 2; ++p) eosr[mt][p] = a.eos_mask[min(8 * mt + 2 * g4 + p, M - 1)];
+
+  float penr[ROWS ? MT : 1][2], ipenr[ROWS ? MT : 1][2], freqr[ROWS ? MT : 1][2];  // (ROWS: the rows' penalties)
+  if constexpr (ROWS) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const float2 pf = *(const float2*)(a.par + min(8 * mt + 2 * g4 + p, M - 1));
+        penr[mt][p] = pf.x; ipenr[mt][p] = 1.f / pf.x; freqr[mt][p] = pf.y;
+      }
+  }
 
   const int units = a.V >> 4, ur = a.ur;
   const int gw = blockIdx.x * kScrWaves + wave;
@@ -421,9 +443,10 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
           const float e = fmaf(rnx[m], fmaf(gam, cs.z, cs.y), rndx[m] * cs.w) * (1.f + 0x1p-20f) +
                           (fabsf(av) + fmaf(fabsf(hq), 256.f, fabsf(lq)) * rsx[m] * cs.x) * 0x1p-21f + 1e-30f;
           const uint16_t* crow = a.counts ? a.counts + (size_t)m * a.seen_stride * 32 : nullptr;
-          ub = head_proc_bound<true>(rbf(av + e), sw[mt][p], c, a.penalty, inv_pen, crow, a.freq_penalty, eosr[mt][p]);
-          const float lb =
-              head_proc_bound<false>(rbf(av - e), sw[mt][p], c, a.penalty, inv_pen, crow, a.freq_penalty, eosr[mt][p]);
+          const float pen = ROWS ? penr[ROWS ? mt : 0][p] : a.penalty, ipen = ROWS ? ipenr[ROWS ? mt : 0][p] : inv_pen;
+          const float frq = ROWS ? freqr[ROWS ? mt : 0][p] : a.freq_penalty;
+          ub = head_proc_bound<true>(rbf(av + e), sw[mt][p], c, pen, ipen, crow, frq, eosr[mt][p]);
+          const float lb = head_proc_bound<false>(rbf(av - e), sw[mt][p], c, pen, ipen, crow, frq, eosr[mt][p]);
           if (a.ub) a.ub[(size_t)m * a.ldu + c] = ub;  // (check mode)
           if constexpr (TOPK) {
             if (a.lbo) a.lbo[(size_t)m * a.ldu + c] = lb;
@@ -518,8 +541,9 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
           valid += __popcll(__ballot(ok));
         }
       }
+      const int top_k = ROWS ? a.par[m].top_k : a.top_k;
       uint32_t prefix = 0u;
-      int kr = a.top_k;
+      int kr = top_k;
       for (int bit = 31; bit >= 0; --bit) {
         const uint32_t want = prefix | (1u << bit), hmask = ~((1u << bit) - 1u);
         int c1 = 0;
@@ -529,7 +553,7 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
         if (c1 >= kr) prefix = want;
         else kr -= c1;
       }
-      if (lane == 0) LBc[m] = valid >= a.top_k ? key2f(prefix) : -INFINITY;
+      if (lane == 0) LBc[m] = valid >= top_k ? key2f(prefix) : -INFINITY;
     }
   }
   if (!TOPK && tid < M * 8) {  // (also without the wait: the other shards' maxima so far cut the recompute,
@@ -623,8 +647,13 @@ __global__ __launch_bounds__(kScrWaves * 64) void head_screen_kernel(HeadScreenA
           const int m = 16 * mb + 4 * g4 + r;
           if (m < M) {
             const uint16_t* crow = a.counts ? a.counts + (size_t)m * a.seen_stride * 32 : nullptr;
-            const float v = head_proc(rbf(acc4[mb][r]), a.seen[(size_t)m * a.seen_stride + (n >> 5)], n, a.penalty,
-                                      crow, a.freq_penalty, a.eos_mask[m]);
+            float pen = a.penalty, frq = a.freq_penalty;
+            if constexpr (ROWS) {
+              const float2 pf = *(const float2*)(a.par + m);
+              pen = pf.x; frq = pf.y;
+            }
+            const float v = head_proc(rbf(acc4[mb][r]), a.seen[(size_t)m * a.seen_stride + (n >> 5)], n, pen, crow, frq,
+                                      a.eos_mask[m]);
             if (a.check && !(v <= a.ub[(size_t)m * a.ldu + n]) && v == v)
               __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if constexpr (TOPK) {
@@ -747,13 +776,16 @@ void launch_head_screen(const HeadScreenArgs& a, int grid, hipStream_t s) {
   if (!head_screen_supported(a.M, a.K, a.V) || a.ur != grid * kScrWaves || (a.V / 16) > kScrMaxUPW * a.ur ||
       a.hKT != a.K / 32 || grid > LOGITS_MAX_PARTS || (pre && (a.K != 2048 || a.normw)))
     throw std::runtime_error("head screen: unsupported shape");
-  const bool topk = a.top_k > 0;
+  const bool topk = a.top_k > 0, rows = a.par != nullptr;
   if (topk && !head_screen_topk_supported(a.M, a.K, a.V, a.top_k, grid))
     throw std::runtime_error("head screen: unsupported top-k shape");
+  if (rows && !(topk && (a.counts || dry_launches())))
+    throw std::runtime_error("head screen: per-row settings need the top-k mode and the counts");
   const int mt = scr_mt(a.M), rpw = (a.M + kScrWaves - 1) / kScrWaves;
   const int rp = pre ? 1 : (rpw <= 1 ? 1 : (rpw <= 2 ? 2 : 4));
+  // (the per-row variant: rows per wave + kScrRowsFlag)
   if (dry_record("head_screen_kernel<" + std::to_string(mt) + ", " + std::to_string(a.K / 64) + ", " +
-                 std::to_string(rp) + ", " + (pre ? "true" : "false") + (topk ? ", true" : "") + ">"))
+                 std::to_string(rp + (rows ? kScrRowsFlag : 0)) + ", " + (pre ? "true" : "false") + (topk ? ", true" : "") + ">"))
     return;
   if (topk && (!a.slots || !a.cand_val || !a.cand_idx || !a.cand_cnt || a.ldc < a.V || (a.check && !a.lbo)))
     throw std::runtime_error("head screen: missing top-k workspace");
@@ -764,7 +796,16 @@ void launch_head_screen(const HeadScreenArgs& a, int grid, hipStream_t s) {
   if (grid % 8) b.spins = 0;  // (the wait's 8 arrival shards need equal shares of the grid)
 #define TTS_SCR(...) \
   hipLaunchKernelGGL((head_screen_kernel<__VA_ARGS__>), dim3(grid), dim3(kScrWaves * 64), lds, s, b)
-  if (topk) {
+  if (rows) {
+    constexpr int F = kScrRowsFlag;
+    if (a.K == 2048) {
+      if (rp == 1) TTS_SCR(1, 32, F + 1, false, true);
+      else if (rp == 2) TTS_SCR(1, 32, F + 2, false, true);
+      else TTS_SCR(2, 32, F + 4, false, true);
+    } else {
+      if (rp == 1) TTS_SCR(1, 64, F + 1, false, true); else TTS_SCR(1, 64, F + 2, false, true);
+    }
+  } else if (topk) {
     if (a.K == 2048) {
       if (rp == 1) TTS_SCR(1, 32, 1, false, true);
       else if (rp == 2) TTS_SCR(1, 32, 2, false, true);

@@ -23,7 +23,18 @@ inline bool dry_record(const std::string& what) {
 
 typedef uint16_t bf16_t;
 
-enum { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_LOGITS = 3 };
+// EPI_LOGITS_ROWS: EPI_LOGITS with the penalties read per row (WgemmArgs::row_par)
+enum { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_LOGITS = 3, EPI_LOGITS_ROWS = 4 };
+
+// One decode row's sampling settings (the per-request slot batch: LmWork::row_par [cap_batch]).
+// The per-row kernels of the captured step read these from device memory where the uniform ones
+// take launch arguments, so a request with other settings needs no recapture.  Every entry always
+// holds valid values (idle rows are computed too): penalty > 0, 1 <= top_k (a greedy row: 1).
+struct RowParams {
+  float penalty, freq_penalty, temperature, top_p;
+  int top_k, eos_id, min_new, sample;
+};
+static_assert(sizeof(RowParams) == 32, "RowParams is 32 bytes");
 
 // Weight layout + decode launch decomposition of one tiled matrix ("stream plan").
 // Work item = (unit of NG n-tiles, K part of KT/ksplit k-tiles); a wave streams its item
@@ -97,6 +108,7 @@ struct StepState {
   uint32_t* epoch;    // [1] step counter (+1 by the finalize of every step: the screened head's keys)
   int eos_id;
   int min_new;
+  const RowParams* par = nullptr;  // [B] per-row eos_id / min_new (and the kernels' settings), or nullptr: the scalars
 };
 
 // Largest tiled weight matrix a wgemm launch streams: one buffer resource with 32-bit byte
@@ -162,6 +174,8 @@ struct WgemmArgs {
   unsigned long long* stamps = nullptr;  // diagnostic build only (TTS_STAMPS): [block][8]
   int csplit = 1;     // 2: each 16-column unit runs as two 8-column halves (twice the workgroups; filled in by launch_wgemm)
   int diag = 0;       // timing diagnostics only (TTS_WGEMM_DIAG): 1 no prologue, 2 no epilogue, 8 barrier before the stream, 64 per-wave norm-end stamps
+  // (last: the fields above keep their kernel-argument offsets, so every other instantiation compiles as before)
+  const RowParams* row_par = nullptr;  // EPI_LOGITS_ROWS: [M] penalty / freq_penalty of each row (counts always set)
 };
 
 struct WgemmPlan {
@@ -234,6 +248,9 @@ struct HeadScreenArgs {
   int* cand_cnt = nullptr;        // [M] entries appended (zero at launch: the list's reader clears it)
   int ldc = 0;                    // >= V
   float* lbo = nullptr;           // check mode: [M][ldu] lower bound of every processed score
+  // per-row top-k mode: penalty, freq_penalty and top_k of row m from par[m] (counts always set;
+  // top_k = the largest top_k the batch admits, for the host checks only)
+  const RowParams* par = nullptr;
 };
 constexpr int HEAD_SCREEN_MAX_TOP_K = 64;  // top-k mode: top_k <= this (and <= the screen's grid)
 bool head_screen_supported(int M, int K, int V);
@@ -331,11 +348,26 @@ struct SampleArgs {
   int* list_cnt = nullptr;
   int list_clear = 0;             // 1: zero list_cnt[b] once read (the screened head appends from zero)
   int vocab = 0;
+  // per-row settings (launch_sample_rows / launch_sample_list_rows): row b reads element
+  // b * row_stride of each array (row_stride 1: plain arrays; 8: the fields of a RowParams table)
+  const float* row_temp = nullptr;
+  const int* row_top_k = nullptr;
+  const float* row_top_p = nullptr;
+  const int* row_sample = nullptr;  // 0: a greedy row (argmax, lowest id on ties; no warper, no draw)
+  int row_stride = 1;
+  const int* part_idx = nullptr;    // dense per-row form: the ids of part_val (a greedy row's argmax partials)
 };
 constexpr int SAMPLE_MAX_TOP_K = 1024;
+inline void sample_rows_from_table(SampleArgs& a, const RowParams* par) {
+  a.row_temp = &par->temperature; a.row_top_k = &par->top_k; a.row_top_p = &par->top_p; a.row_sample = &par->sample;
+  a.row_stride = (int)(sizeof(RowParams) / 4);
+}
 void launch_sample(const SampleArgs& a, int B, hipStream_t s);
 // the same draw from per-row candidate lists that hold (at least) every entry of the top-k set
 void launch_sample_list(const SampleArgs& a, int B, hipStream_t s);
+// the per-row forms: temperature / top_k / top_p / sample of row b from the row_* arrays
+void launch_sample_rows(const SampleArgs& a, int B, hipStream_t s);
+void launch_sample_list_rows(const SampleArgs& a, int B, hipStream_t s);
 
 void launch_bump_epoch(uint32_t* epoch, hipStream_t s);  // *epoch += 1 (a decode step without finalize)
 void launch_finalize_greedy(const float* part_val, const int* part_idx, int part_stride,

@@ -292,6 +292,7 @@ void lm_load(Engine* e, const tts_lm_config* cfgp, const tts_tensor_desc* t, int
   w.row_idx.alloc((size_t)R * 4);
   w.st_int.alloc((size_t)B * 8 * 4 + 64);  // (>= the st_zeros(B) ints of the layout, lm_step.h)
   w.row_seed.alloc((size_t)B * 8);
+  w.row_par.alloc((size_t)B * sizeof(RowParams));
   w.seen.alloc((size_t)B * (V / 32 + 1) * 4);
   w.out_cap = S;
   w.out_ids.alloc((size_t)B * S * 4);

@@ -66,13 +66,28 @@ TTS_DEV void bitonic_desc(unsigned long long* a, int n) {
 // lm_head_screen.hip) instead of the dense row of a.V processed logits; entry i stands for id
 // list_idx[i], everything else is the dense form's code: the same values sort into the same
 // order, so the draw is the dense row's.
-template <bool LIST>
+//
+// ROWS: temperature, top_k, top_p and the sample flag are row b's own (a.row_*, SampleArgs), the
+// rest of the body unchanged: a sampled row draws what the uniform kernel draws with the same
+// scalars.  A greedy row (sample 0) bypasses the warpers and the draw: its token is the argmax by
+// float comparison, lowest id on ties (finalize_row's reduction) — over the lm_head's argmax
+// partials (dense form; read before partial 0 is overwritten with the token), or the dense row
+// itself when there are none, or the row's candidate list (list form).  No temperature touches a
+// greedy row: v / T can round two distinct scores to one value, and the sort key orders -0.0
+// below +0.0 where the float comparison does not.
+template <bool LIST, bool ROWS>
 TTS_DEV void sample_body(const SampleArgs& a) {
   __shared__ unsigned long long cand[SMP_CMAX];
   __shared__ unsigned hist[256];
   __shared__ int s_cnt;
   __shared__ uint32_t s_thr;
   const int b = blockIdx.x, tid = threadIdx.x;
+  float temperature = a.temperature, top_p = a.top_p;
+  int top_k = a.top_k, do_sample = 1;
+  if constexpr (ROWS) {
+    const size_t o = (size_t)b * a.row_stride;
+    temperature = a.row_temp[o]; top_k = a.row_top_k[o]; top_p = a.row_top_p[o]; do_sample = a.row_sample[o];
+  }
   int V = a.V;  // entries of the row
   if constexpr (LIST) {
     V = min(a.list_cnt[b], a.V);
@@ -98,11 +113,44 @@ TTS_DEV void sample_body(const SampleArgs& a) {
   const float* l = a.logits + (size_t)b * a.ldl;
   const int* lid = LIST ? a.list_idx + (size_t)b * a.ldl : nullptr;
   auto id_of = [&](int i) { return LIST ? (unsigned)lid[i] : (unsigned)i; };
-  const bool scale = a.temperature != 1.0f;
-  auto sval = [&](int i) { const float v = l[i]; return scale ? v / a.temperature : v; };
+  if constexpr (ROWS) {
+    if (!do_sample) {  // (uniform over the workgroup)
+      __shared__ float gv[SMP_THREADS / 64];
+      __shared__ int gi[SMP_THREADS / 64];
+      float v = -INFINITY;
+      int i = 0x7fffffff;
+      auto merge = [&](float v2, int i2) { if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; } };
+      if (!LIST && a.part_val != nullptr && a.part_idx != nullptr && a.nparts > 0) {
+        for (int p = tid; p < a.nparts; p += SMP_THREADS)
+          merge(a.part_val[(size_t)b * a.part_stride + p], a.part_idx[(size_t)b * a.part_stride + p]);
+      } else {
+        for (int p = tid; p < V; p += SMP_THREADS) merge(l[p], (int)id_of(p));
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float v2 = __shfl_xor(v, o, 64);
+        const int i2 = __shfl_xor(i, o, 64);
+        merge(v2, i2);
+      }
+      if ((tid & 63) == 0) { gv[tid >> 6] = v; gi[tid >> 6] = i; }
+      __syncthreads();  // (every partial is read: partial 0 may be overwritten below)
+      if (tid == 0) {
+        for (int w = 1; w < SMP_THREADS / 64; ++w) merge(gv[w], gi[w]);
+        const int tok = (i == 0x7fffffff) ? 0 : i;  // (finalize's guard for a row without a pick)
+        if (a.out_part_idx) {
+          a.out_part_val[(size_t)b * a.part_stride] = 0.f;
+          a.out_part_idx[(size_t)b * a.part_stride] = tok;
+        }
+        if (a.tokens) a.tokens[b] = tok;
+      }
+      return;
+    }
+  }
+  const bool scale = temperature != 1.0f;
+  auto sval = [&](int i) { const float v = l[i]; return scale ? v / temperature : v; };
   // (the k of the dense row the list stands for: a list shorter than k keeps all of its entries)
-  const int k = LIST ? ((a.top_k > 0 && a.top_k < a.vocab) ? min(a.top_k, V) : V)
-                     : ((a.top_k > 0 && a.top_k < V) ? a.top_k : V);
+  const int k = LIST ? ((top_k > 0 && top_k < a.vocab) ? min(top_k, V) : V)
+                     : ((top_k > 0 && top_k < V) ? top_k : V);
 
   // ---- threshold: k-th largest of the lm_head partial maxima (a lower bound), or exact
   uint32_t thr = 0u;  // keep keys >= thr
@@ -112,7 +160,7 @@ TTS_DEV void sample_body(const SampleArgs& a) {
     while (np2 < a.nparts) np2 <<= 1;
     for (int i = tid; i < np2; i += SMP_THREADS) {
       const float v = i < a.nparts ? a.part_val[(size_t)b * a.part_stride + i] : -INFINITY;
-      cand[i] = ((unsigned long long)okey(scale ? v / a.temperature : v) << 32) | (unsigned)i;
+      cand[i] = ((unsigned long long)okey(scale ? v / temperature : v) << 32) | (unsigned)i;
     }
     __syncthreads();
     bitonic_desc(cand, np2);
@@ -189,12 +237,12 @@ TTS_DEV void sample_body(const SampleArgs& a) {
     // top-p over the ascending order: drop while the cumulative probability <= 1 - p,
     // never the largest
     int nkeep = nk;
-    if (a.top_p < 1.0f) {
+    if (top_p < 1.0f) {
       float cum = 0.f;
       int first_kept = 0;  // in ascending order: index nk-1-i
       for (int i = nk - 1; i >= 1; --i) {
         cum += expf(okey_inv((uint32_t)(cand[i] >> 32)) - mx) / z;
-        if (cum <= 1.0f - a.top_p) first_kept = nk - i;
+        if (cum <= 1.0f - top_p) first_kept = nk - i;
         else break;
       }
       nkeep = nk - first_kept;
@@ -224,8 +272,10 @@ TTS_DEV void sample_body(const SampleArgs& a) {
   }
 }
 
-__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) { sample_body<false>(a); }
-__global__ __launch_bounds__(SMP_THREADS) void sample_list_kernel(SampleArgs a) { sample_body<true>(a); }
+__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) { sample_body<false, false>(a); }
+__global__ __launch_bounds__(SMP_THREADS) void sample_list_kernel(SampleArgs a) { sample_body<true, false>(a); }
+__global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleArgs a) { sample_body<false, true>(a); }
+__global__ __launch_bounds__(SMP_THREADS) void sample_list_rows_kernel(SampleArgs a) { sample_body<true, true>(a); }
 
 }  // namespace
 
@@ -242,6 +292,29 @@ void launch_sample_list(const SampleArgs& a, int B, hipStream_t s) {
   b.part_val = nullptr;  // (the list is the candidate set: no partial maxima to bound it)
   b.nparts = 0;
   hipLaunchKernelGGL(sample_list_kernel, dim3(B), dim3(SMP_THREADS), 0, s, b);
+}
+
+static void require_row_arrays(const SampleArgs& a) {
+  if (!a.row_temp || !a.row_top_k || !a.row_top_p || !a.row_sample || a.row_stride < 1)
+    throw std::runtime_error("per-row sampler: missing settings arrays");
+}
+
+void launch_sample_rows(const SampleArgs& a, int B, hipStream_t s) {
+  if (dry_record("sample_rows_kernel")) return;
+  require_row_arrays(a);
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(SMP_THREADS), 0, s, a);
+}
+
+void launch_sample_list_rows(const SampleArgs& a, int B, hipStream_t s) {
+  if (dry_record("sample_list_rows_kernel")) return;
+  require_row_arrays(a);
+  if (!a.logits || !a.list_idx || !a.list_cnt || a.vocab < 1 || a.V < 1 || a.V > a.ldl)
+    throw std::runtime_error("list sampler: missing list");
+  SampleArgs b = a;
+  b.part_val = nullptr;  // (the list is the candidate set: no partial maxima to bound it)
+  b.part_idx = nullptr;
+  b.nparts = 0;
+  hipLaunchKernelGGL(sample_list_rows_kernel, dim3(B), dim3(SMP_THREADS), 0, s, b);
 }
 
 }  // namespace tts

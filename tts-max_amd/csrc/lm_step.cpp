@@ -38,6 +38,7 @@ StepState step_state_row(const StepState& st, int slot) {
   StepState one = st;
   one.tokens += slot; one.pos += slot; one.gen_count += slot; one.limit += slot;
   one.done += slot; one.eos_mask += slot; one.row_seed += slot;
+  if (one.par) one.par += slot;
   one.seen += (size_t)slot * st.seen_stride;
   one.out_ids += (size_t)slot * st.out_stride;
   if (one.counts) one.counts += (size_t)slot * st.seen_stride * 32;
@@ -142,6 +143,7 @@ bool Ctx::gemm(const Gemm& g) {
         if (a.part_idx) a.part_idx += (size_t)r0 * a.part_stride;
         if (a.logits_out) a.logits_out += (size_t)r0 * a.ldl;
         if (a.counts) a.counts += (size_t)r0 * a.seen_stride * 32;
+        if (a.row_par) a.row_par += r0;
       }
     }
     a.x = xin; a.M = m; a.K = K; a.ldx = K;
@@ -292,6 +294,7 @@ StepState Ctx::state(int B, int eos, int min_new) {
   st.epoch = w.epoch.as<uint32_t>();
   st.out_ids = w.out_ids.as<int>(); st.out_stride = w.out_cap;
   st.eos_id = eos; st.min_new = min_new;
+  st.par = nullptr;  // (the caller's, in a per-request slot batch)
   return st;
 }
 
@@ -347,6 +350,36 @@ void Ctx::head_and_pick(const bf16_t* xin, int B, const StepState& st, const tts
   finalize(nparts, B, st);
 }
 
+// The per-request batch's pick: every row's settings from st.par (device memory), one kernel set
+// for any mix of greedy and sampled rows.  Batches of 17..32 rows always take the full head: the
+// screen's top-k mode covers 1..16 rows (8 at hidden 4096).
+bool Ctx::rows_screen_ok(int B, int max_top_k) const {
+  return M.head_grid && head_screen_topk_supported(B, c.hidden_size, c.vocab_size, std::max(1, max_top_k), M.head_grid);
+}
+void Ctx::head_and_pick_rows(const bf16_t* xin, int B, const StepState& st, bool dense, int max_top_k) {
+  TTS_REQUIRE(st.par && st.counts, "per-row step without its settings table");
+  tts_gen_params gp{};  // (neutral: the per-row kernels read none of it)
+  gp.do_sample = 1; gp.repetition_penalty = 1.f; gp.temperature = 1.f; gp.top_k = 1; gp.top_p = 1.f;
+  if (!dense && rows_screen_ok(B, max_top_k)) {
+    screened_head_parts(xin, B, st, gp, std::max(1, max_top_k), st.par);
+    SampleArgs sa = sample_args(st, gp, true);
+    sample_rows_from_table(sa, st.par);
+    launch_sample_list_rows(sa, B, s);
+    finalize(1, B, st);
+    return;
+  }
+  TTS_REQUIRE(B <= kPrefillChunk, "batch larger than one GEMM chunk");
+  const int nparts = plan_wgemm(B, c.vocab_size, c.hidden_size, EPI_LOGITS_ROWS, e->num_cu).grid;
+  WgemmArgs ex = head_epilogue_args(st, gp);
+  ex.row_par = st.par;
+  lm_head_pick(xin, B, ex, EPI_LOGITS_ROWS);
+  SampleArgs sa = sample_args(st, gp, false, nparts);
+  sa.part_idx = w.lpart_i.as<int>();  // (a greedy row's argmax partials)
+  sample_rows_from_table(sa, st.par);
+  launch_sample_rows(sa, B, s);
+  finalize(1, B, st);
+}
+
 // the sampled pick through the same screen (its top-k mode): the candidates of the top-k set,
 // recomputed exactly, into per-row lists; the list sampler draws from them and leaves the token
 // as the one "partial" finalize reads.  The ids of the full-head sampled step.
@@ -357,7 +390,8 @@ void Ctx::screened_sample(const bf16_t* xin, int B, const StepState& st, const t
 // the screened head's launch (int8 screen + exact recompute of the units that can hold the
 // argmax); returns the number of argmax partials per row.  top_k > 0: its top-k mode (the
 // units that can hold a top-k candidate, into the candidate lists; no argmax partials)
-int Ctx::screened_head_parts(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp, int top_k) {
+int Ctx::screened_head_parts(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp, int top_k,
+                             const RowParams* par) {
   const int HID = c.hidden_size, V = c.vocab_size;
   HeadScreenArgs a;
   a.M = B; a.K = HID; a.ldx = HID; a.V = V;
@@ -393,6 +427,7 @@ int Ctx::screened_head_parts(const bf16_t* xin, int B, const StepState& st, cons
     a.slots = w.hslot.as<unsigned long long>();
     a.cand_val = w.hcv.as<float>(); a.cand_idx = w.hci.as<int>(); a.cand_cnt = w.hcn.as<int>(); a.ldc = V;
     if (a.check) a.lbo = w.hlo.as<float>();
+    a.par = par;
   }
   static const int diag = env_int("TTS_HEAD_SCREEN_DIAG", 0);
   a.diag = diag;
@@ -451,7 +486,7 @@ void Ctx::prefill_all(const int32_t* ids, const std::vector<int>& start, const s
 // without a GPU: the step's own code (Ctx::layers + head_and_pick) run with the launchers in
 // dry-run mode (lm_kernels.h dry_launches), nothing allocated.  Unique launches in first-seen
 // order, one per line (wgemm instantiations as wgemm_inst_name writes them).
-std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k) {
+std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k, bool per_row) {
   TTS_REQUIRE(c.head_dim == 64 || c.head_dim == 128, "head_dim must be 64 or 128");
   TTS_REQUIRE(c.num_heads == 4 * c.num_kv_heads && c.num_layers >= 1, "bad config");
   TTS_REQUIRE(rows >= 1 && rows <= 64 && num_cu >= 1, "rows in [1, 64], num_cu >= 1");
@@ -477,13 +512,19 @@ std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k
   try {
     Ctx X(&e, nullptr);
     X.layers(rows, nullptr, nullptr, true);
-    const StepState st = X.state(rows, 0, 0);
+    StepState st = X.state(rows, 0, 0);
     tts_gen_params gp{};
     gp.repetition_penalty = 1.1f;
     if (top_k > 0) {  // a sampled step
       gp.do_sample = 1; gp.temperature = 0.8f; gp.top_k = top_k; gp.top_p = 1.0f;
     }
-    X.head_and_pick(nullptr, rows, st, gp);
+    if (per_row) {  // (placeholder addresses, as the weights': never dereferenced)
+      st.par = (const RowParams*)next();
+      st.counts = (uint16_t*)next();
+      X.head_and_pick_rows(nullptr, rows, st, !X.rows_screen_ok(rows, top_k), top_k);
+    } else {
+      X.head_and_pick(nullptr, rows, st, gp);
+    }
   } catch (...) {
     dry_launches() = nullptr;
     e.w.kpart.bytes = 0;

@@ -72,8 +72,8 @@ struct Ctx {
     gemm(g);
   }
   // lm_head over RMSNorm(x, final norm): the processing epilogue + argmax partials, or plain logits
-  void lm_head_pick(const bf16_t* x, int rows, const WgemmArgs& epilogue) {
-    Gemm g{x, rows, c.hidden_size, M.lm_head, c.vocab_size, EPI_LOGITS};
+  void lm_head_pick(const bf16_t* x, int rows, const WgemmArgs& epilogue, int epi = EPI_LOGITS) {
+    Gemm g{x, rows, c.hidden_size, M.lm_head, c.vocab_size, epi};
     g.normw = M.final_norm; g.extra = &epilogue;
     gemm(g);
   }
@@ -95,8 +95,15 @@ struct Ctx {
   // the sampler's: over the dense logits (nparts workgroup maxima a row) or the screen's lists
   SampleArgs sample_args(const StepState& st, const tts_gen_params& gp, bool lists, int nparts = 0);
   void head_and_pick(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp);
+  // the per-request batch's pick (st.par, st.counts set): the screen's per-row top-k form + the
+  // per-row list sampler where the rows and max_top_k fit it and !dense, else the per-row full head
+  // + the per-row dense sampler
+  bool rows_screen_ok(int B, int max_top_k) const;
+  void head_and_pick_rows(const bf16_t* xin, int B, const StepState& st, bool dense, int max_top_k);
   void screened_sample(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp);
-  int screened_head_parts(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp, int top_k = 0);
+  // (par: the per-row variant of the top-k mode, top_k = the batch's largest)
+  int screened_head_parts(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp, int top_k = 0,
+                          const RowParams* par = nullptr);
 
   // Prefill nb whole sequences (ids concatenated; KV slots slot_base..) in one pass: row setup +
   // layers, and (gather_row >= 0) their last rows into w.last_x from that row on.  Returns each

@@ -22,6 +22,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TTS_LIB_PATH") or os.path.join(_HERE, "libtts_mi355x.so")
 
 TTS_OK = 0
+TTS_E_INVALID = 1
+TTS_E_STATE = 4
 DT_F32, DT_BF16, DT_F16, DT_I32, DT_I64 = 0, 1, 2, 3, 4
 EPI_STORE, EPI_RESID, EPI_SWIGLU = 0, 1, 2
 
@@ -61,6 +63,10 @@ EXPORTED_SYMBOLS = (
     "tts_op_pgemm",
     "tts_op_sample",
     "tts_op_sample_list",
+    "tts_op_sample_rows",
+    "tts_slots_open_per_request",
+    "tts_slots_add_params",
+    "tts_debug_step_plan_rows",
     "tts_op_rmsnorm",
     "tts_op_gemm_f32",
     "tts_op_attn_prefill",
@@ -170,6 +176,8 @@ def load_library() -> ctypes.CDLL:
         "tts_slots_open": (I32, [P, ctypes.POINTER(GenParams), I32, P]),
         "tts_slots_add": (I32, [P, I32, pi32, I32, I32]),
         "tts_slots_add_seeded": (I32, [P, I32, pi32, I32, I32, ctypes.c_uint64]),
+        "tts_slots_open_per_request": (I32, [P, ctypes.POINTER(GenParams), I32, P]),
+        "tts_slots_add_params": (I32, [P, I32, pi32, I32, I32, ctypes.POINTER(GenParams), ctypes.POINTER(U64)]),
         "tts_slots_step": (I32, [P, I32, pi32]),
         "tts_slots_read": (I32, [P, I32, pi32, I32, pi32, pi32]),
         "tts_slots_release": (I32, [P, I32]),
@@ -192,12 +200,14 @@ def load_library() -> ctypes.CDLL:
         "tts_op_pgemm": (I32, [P, I32, I32, P, I32, P, I32, P, I32, P]),
         "tts_op_sample": (I32, [P, I32, I32, F32, I32, F32, ctypes.c_uint64, I32, P, I32, P, P, P]),
         "tts_op_sample_list": (I32, [P, P, P, I32, I32, I32, F32, I32, F32, ctypes.c_uint64, I32, P, P, P]),
+        "tts_op_sample_rows": (I32, [P, P, P, I32, I32, I32, P, P, P, P, P, I32, P, P, I32, P, P, P]),
         "tts_op_rmsnorm": (I32, [P, P, F32, P, I32, I32, P]),
         "tts_op_gemm_f32": (I32, [P, I32, I32, I32, P, I32, P, P, I32, P, I32, P]),
         "tts_op_attn_prefill": (I32, [P, I32, pi32, pi32, pi32, I32, I32, P, P, I32, P, P, I32, I32, I32, F32, P, P, P]),
         "tts_op_attn_decode": (I32, [P, P, I32, I32, I32, P, P, I32, P, P, I32, P, P, I32, I32, I32, F32, P, P]),
         "tts_debug_step_plan": (I32, [ctypes.POINTER(LmConfig), I32, I32, ctypes.c_char_p, I32]),
         "tts_debug_step_plan_sampled": (I32, [ctypes.POINTER(LmConfig), I32, I32, I32, ctypes.c_char_p, I32]),
+        "tts_debug_step_plan_rows": (I32, [ctypes.POINTER(LmConfig), I32, I32, I32, ctypes.c_char_p, I32]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("TTS_LIB_PATH") and not hasattr(lib, name):

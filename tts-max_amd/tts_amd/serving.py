@@ -17,6 +17,13 @@ backed by the engine's slot API (``tts_slots_*``):
 
 Settings (penalty, EOS, min_tokens, sampling) are per batcher, as the reference's
 InferenceSettings are per process; requests differ in prompt and max_tokens.
+
+``per_request=True`` (``ContinuousBatcher``, ``LLM``) lifts that: every request may carry its
+own ``RequestSettings`` (``tts_slots_open_per_request`` / ``tts_slots_add_params``: the captured
+step reads each row's settings from a device table), so callers that differ in temperature,
+top_k, top_p, penalties, min_tokens or stop id share one running batch, as vLLM's do.  Each
+request's tokens still equal a uniform batcher's with that request's settings and seed
+(tests/test_gpu_slots_per_request.py).
 """
 
 from __future__ import annotations
@@ -38,8 +45,40 @@ try:  # the HTTP front end is optional (fastapi / pydantic are in the image)
     class GenerateRequest(_BaseModel):
         prompt_token_ids: list[int]
         max_tokens: int = 16
+        # the request's own settings (a per-request batcher only; all None: the batcher's defaults)
+        temperature: float | None = None
+        top_k: int | None = None
+        top_p: float | None = None
+        repetition_penalty: float | None = None
+        frequency_penalty: float | None = None
+        min_new_tokens: int | None = None
+        eos_token_id: int | None = None
+        seed: int | None = None
 except ImportError:  # pragma: no cover
     GenerateRequest = None
+
+
+@dataclasses.dataclass
+class RequestSettings:
+    """One request's sampling settings (a per-request batcher).  temperature 0 = greedy
+    (do_sample = temperature > 0, inferencing.py:100)."""
+    temperature: float = 0.0
+    top_k: int = 50
+    top_p: float = 1.0
+    repetition_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    min_new_tokens: int = 0
+    eos_token_id: int = -1
+
+    @property
+    def do_sample(self) -> bool:
+        return self.temperature > 0
+
+    def gen_params(self) -> "_lib.GenParams":
+        return _lib.GenParams(max_length=0, min_new_tokens=int(self.min_new_tokens), eos_token_id=int(self.eos_token_id),
+                              do_sample=1 if self.do_sample else 0, repetition_penalty=float(self.repetition_penalty),
+                              temperature=float(self.temperature), top_p=float(self.top_p), top_k=int(self.top_k),
+                              seed=0, frequency_penalty=float(self.frequency_penalty))
 
 
 @dataclasses.dataclass
@@ -48,18 +87,20 @@ class _Req:
     max_new: int
     future: Future
     seed: int | None = None  # the request's own sampling key (vLLM SamplingParams.seed)
+    settings: RequestSettings | None = None  # the request's own settings (per-request batcher)
 
 
 class ContinuousBatcher:
     def __init__(self, lm, n_slots: int, eos_token_id: int = -1, min_new_tokens: int = 0,
                  repetition_penalty: float = 1.0, do_sample: bool = False, temperature: float = 1.0,
                  top_k: int = 50, top_p: float = 1.0, frequency_penalty: float = 0.0, seed: int | None = None,
-                 chunk: int = 8):
+                 chunk: int = 8, per_request: bool = False):
         if n_slots < 1 or n_slots > lm.max_batch:
             raise ValueError(f"n_slots {n_slots} outside [1, max_batch={lm.max_batch}]")
-        if do_sample and seed is None:
+        if (do_sample or per_request) and seed is None:
             seed = int(torch.randint(0, 2**62, (1,)).item())
         self.lm, self.S, self.chunk = lm, n_slots, chunk
+        self.per_request = per_request  # requests may carry their own RequestSettings (the rest: defaults)
         self._p = _lib.GenParams(max_length=0, min_new_tokens=min_new_tokens, eos_token_id=eos_token_id,
                                  do_sample=1 if do_sample else 0, repetition_penalty=repetition_penalty,
                                  temperature=temperature, top_p=top_p, top_k=top_k, seed=seed or 0,
@@ -75,16 +116,20 @@ class ContinuousBatcher:
         self.error: BaseException | None = None  # set when the engine loop failed (batcher dead)
 
     # ------------------------------------------------------------------ requests -------
-    def submit(self, prompt_ids: Sequence[int], max_new_tokens: int, seed: int | None = None) -> Future:
+    def submit(self, prompt_ids: Sequence[int], max_new_tokens: int, seed: int | None = None,
+               settings: RequestSettings | None = None) -> Future:
         """Queues a request.  `seed` fixes the request's sampling stream (vLLM per-request
-        seed); None draws a fresh stream per request from the batcher's seed."""
+        seed); None draws a fresh stream per request from the batcher's seed.  `settings`: the
+        request's own sampling settings (a per_request batcher only; None: the batcher's)."""
+        if settings is not None and not self.per_request:
+            raise ValueError("per-request settings need ContinuousBatcher(..., per_request=True)")
         fut: Future = Future()
         if self.error is not None:
             fut.set_exception(RuntimeError(f"batcher stopped after an engine error: {self.error}"))
             return fut
         with self._lock:
             self._queue.append(_Req(list(map(int, prompt_ids)), int(max_new_tokens), fut,
-                                    None if seed is None else int(seed) & (2**64 - 1)))
+                                    None if seed is None else int(seed) & (2**64 - 1), settings))
         self._wake.set()
         return fut
 
@@ -93,11 +138,15 @@ class ContinuousBatcher:
             return bool(self._queue) or any(r is not None for r in self._slot_req)
 
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int | Sequence[int],
-                 seed: int | None = None) -> list[list[int]]:
-        """Blocking: all prompts through the continuous batch, results in order."""
+                 seed: int | None | Sequence[int | None] = None,
+                 settings: RequestSettings | None | Sequence[RequestSettings | None] = None) -> list[list[int]]:
+        """Blocking: all prompts through the continuous batch, results in order.  seed and
+        settings: one for all prompts, or a list with one entry per prompt."""
         if isinstance(max_new_tokens, int):
             max_new_tokens = [max_new_tokens] * len(prompts)
-        futs = [self.submit(p, n, seed) for p, n in zip(prompts, max_new_tokens)]
+        seeds = list(seed) if isinstance(seed, (list, tuple)) else [seed] * len(prompts)
+        sets = list(settings) if isinstance(settings, (list, tuple)) else [settings] * len(prompts)
+        futs = [self.submit(p, n, sd, st) for p, n, sd, st in zip(prompts, max_new_tokens, seeds, sets)]
         if self._thread is None:  # no background loop: drive it here
             while not all(f.done() for f in futs):
                 self._run_guarded()
@@ -106,7 +155,8 @@ class ContinuousBatcher:
     # ------------------------------------------------------------------ engine loop ----
     def _open(self):
         if not self._opened or self.lm._slot_batcher is not self:
-            _lib.check(self.lm._lib.tts_slots_open(self.lm._h, ctypes.byref(self._p), self.S, None))
+            opener = self.lm._lib.tts_slots_open_per_request if self.per_request else self.lm._lib.tts_slots_open
+            _lib.check(opener(self.lm._h, ctypes.byref(self._p), self.S, None))
             self.lm._slot_batcher = self
             self._opened = True
 
@@ -148,7 +198,12 @@ class ContinuousBatcher:
                     r = self._queue.pop(0)
                     arr = np.ascontiguousarray(np.asarray(r.prompt, dtype=np.int32))
                     try:
-                        if r.seed is None:
+                        if r.settings is not None:
+                            gp = r.settings.gen_params()
+                            sd = None if r.seed is None else ctypes.byref(ctypes.c_uint64(r.seed))
+                            _lib.check(L.tts_slots_add_params(h, s, arr.ctypes.data_as(pi32), len(arr), r.max_new,
+                                                              ctypes.byref(gp), sd))
+                        elif r.seed is None:
                             _lib.check(L.tts_slots_add(h, s, arr.ctypes.data_as(pi32), len(arr), r.max_new))
                         else:
                             _lib.check(L.tts_slots_add_seeded(h, s, arr.ctypes.data_as(pi32), len(arr), r.max_new,
@@ -214,13 +269,15 @@ class RequestOutput:
 
 class LLM:
     """vLLM-shaped facade (inferencing.py:75-92): one ContinuousBatcher per distinct
-    SamplingParams configuration."""
+    SamplingParams configuration, or (per_request=True) one batcher that serves every
+    SamplingParams, each request with its own settings in the shared batch."""
 
-    def __init__(self, lm, n_slots: int = 16, chunk: int = 8):
-        self.lm, self.n_slots, self.chunk = lm, n_slots, chunk
+    def __init__(self, lm, n_slots: int = 16, chunk: int = 8, per_request: bool = False):
+        self.lm, self.n_slots, self.chunk, self.per_request = lm, n_slots, chunk, per_request
         self._batchers: dict[tuple, ContinuousBatcher] = {}
 
-    def _batcher(self, sp: Any) -> ContinuousBatcher:
+    @staticmethod
+    def _settings_key(sp: Any) -> tuple:
         temperature = float(getattr(sp, "temperature", 1.0) or 0.0)
         stop = list(getattr(sp, "stop_token_ids", None) or [])
         if len(stop) > 1:
@@ -230,9 +287,28 @@ class LLM:
         top_k = int(getattr(sp, "top_k", -1) or -1)
         if temperature > 0 and top_k <= 0:
             raise NotImplementedError("full-vocabulary sampling (vLLM top_k=-1) is not built; pass top_k")
-        key = (temperature, stop[0] if stop else -1, int(getattr(sp, "min_tokens", 0) or 0),
-               float(getattr(sp, "repetition_penalty", 1.0) or 1.0), top_k, float(getattr(sp, "top_p", 1.0) or 1.0),
-               float(getattr(sp, "frequency_penalty", 0.0) or 0.0))
+        return (temperature, stop[0] if stop else -1, int(getattr(sp, "min_tokens", 0) or 0),
+                float(getattr(sp, "repetition_penalty", 1.0) or 1.0), top_k, float(getattr(sp, "top_p", 1.0) or 1.0),
+                float(getattr(sp, "frequency_penalty", 0.0) or 0.0))
+
+    @classmethod
+    def _request_settings(cls, sp: Any) -> RequestSettings:
+        key = cls._settings_key(sp)
+        return RequestSettings(temperature=key[0], eos_token_id=key[1], min_new_tokens=key[2], repetition_penalty=key[3],
+                               top_k=key[4] if key[4] > 0 else 50, top_p=key[5], frequency_penalty=key[6])
+
+    def _shared_batcher(self) -> ContinuousBatcher:
+        old = self._batchers.get(())
+        if old is not None and old.error is not None:
+            old.close()
+            del self._batchers[()]
+        if () not in self._batchers:
+            self._batchers[()] = ContinuousBatcher(self.lm, self.n_slots, chunk=self.chunk, per_request=True)
+        return self._batchers[()]
+
+    def _batcher(self, sp: Any) -> ContinuousBatcher:
+        key = self._settings_key(sp)
+        temperature, top_k = key[0], key[4]
         old = self._batchers.get(key)
         if old is not None and old.error is not None:  # a batcher that died on an engine error:
             old.close()                                 # replace it instead of failing every later call
@@ -252,6 +328,15 @@ class LLM:
         prompts = prompt_token_ids
         if prompts and isinstance(prompts[0], (int, np.integer)):
             prompts = [prompts]
+        if self.per_request:  # one batcher; sampling_params may be a list, one entry per prompt (as vLLM)
+            sps = list(sampling_params) if isinstance(sampling_params, (list, tuple)) else [sampling_params] * len(prompts)
+            if len(sps) != len(prompts):
+                raise ValueError("sampling_params: one entry per prompt")
+            outs = self._shared_batcher().generate(
+                prompts, [int(getattr(sp, "max_tokens", 16)) for sp in sps],
+                seed=[getattr(sp, "seed", None) for sp in sps], settings=[self._request_settings(sp) for sp in sps])
+            return [RequestOutput(prompt_token_ids=list(p), outputs=[CompletionOutput(token_ids=o)])
+                    for p, o in zip(prompts, outs)]
         b = self._batcher(sampling_params)
         outs = b.generate(prompts, int(getattr(sampling_params, "max_tokens", 16)),
                           seed=getattr(sampling_params, "seed", None))
@@ -272,7 +357,18 @@ def create_app(batcher: ContinuousBatcher):
     async def generate(req: GenerateRequest):
         if not req.prompt_token_ids or req.max_tokens < 1:
             raise HTTPException(status_code=400, detail="empty prompt or max_tokens < 1")
-        fut = batcher.submit(req.prompt_token_ids, req.max_tokens)
+        own = {k: getattr(req, k) for k in ("temperature", "top_k", "top_p", "repetition_penalty", "frequency_penalty",
+                                            "min_new_tokens", "eos_token_id") if getattr(req, k) is not None}
+        settings = None
+        if own:
+            if not batcher.per_request:
+                raise HTTPException(status_code=400, detail="this server's batcher takes no per-request settings")
+            p = batcher._p  # fields not given: the batcher's defaults
+            base = RequestSettings(temperature=p.temperature if p.do_sample else 0.0, top_k=p.top_k, top_p=p.top_p,
+                                   repetition_penalty=p.repetition_penalty, frequency_penalty=p.frequency_penalty,
+                                   min_new_tokens=p.min_new_tokens, eos_token_id=p.eos_token_id)
+            settings = dataclasses.replace(base, **own)
+        fut = batcher.submit(req.prompt_token_ids, req.max_tokens, seed=req.seed, settings=settings)
         try:
             ids = await asyncio.wrap_future(fut)
         except Exception as ex:  # engine rejected the request

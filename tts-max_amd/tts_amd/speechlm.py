@@ -81,15 +81,19 @@ def lm_config(arch: configs.LmArch, max_batch: int = 1, max_seq_len: int = 2048)
         max_seq_len=max_seq_len)
 
 
-def step_plan(arch: configs.LmArch, rows: int, num_cu: int = 256, top_k: int | None = None) -> list[str]:
+def step_plan(arch: configs.LmArch, rows: int, num_cu: int = 256, top_k: int | None = None,
+              per_row: bool = False) -> list[str]:
     """The kernels one decode step over `rows` rows launches (tts_debug_step_plan: the
     engine's step code in dry-run mode; no GPU needed): unique, in first-seen order.
     top_k: the plan of a sampled step with that top_k (tts_debug_step_plan_sampled) instead of
-    the greedy step's."""
+    the greedy step's.  per_row: the per-request slot batch's step (tts_debug_step_plan_rows),
+    top_k = the largest top_k it admitted (default 1)."""
     lib = _lib.load_library()
     cfg = lm_config(arch, max_batch=max(rows, 1), max_seq_len=2048)
     buf = ctypes.create_string_buffer(1 << 16)
-    if top_k is None:
+    if per_row:
+        _lib.check(lib.tts_debug_step_plan_rows(ctypes.byref(cfg), rows, num_cu, top_k or 1, buf, len(buf)))
+    elif top_k is None:
         _lib.check(lib.tts_debug_step_plan(ctypes.byref(cfg), rows, num_cu, buf, len(buf)))
     else:
         _lib.check(lib.tts_debug_step_plan_sampled(ctypes.byref(cfg), rows, num_cu, top_k, buf, len(buf)))
