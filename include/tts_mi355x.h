@@ -91,7 +91,7 @@ typedef struct {
   float rope_low_freq_factor;  /* 1                                                  */
   float rope_high_freq_factor; /* 4                                                  */
   int32_t rope_original_max_position; /* 8192                                        */
-  int32_t max_batch;           /* KV-cache slots (sequences resident at once)        */
+  int32_t max_batch;           /* KV-cache slots (sequences resident at once), 1..256 */
   int32_t max_seq_len;         /* KV capacity per sequence (prompt + generated)      */
 } tts_lm_config;
 
@@ -163,7 +163,14 @@ tts_status tts_generate_read(tts_engine* e, int32_t* out_ids, int32_t out_stride
  * generating), tts_slots_read returns a slot's new tokens so far and whether it stopped,
  * tts_slots_release frees the slot (stopping it first if it is still running).  Each
  * sequence's tokens equal a batch-1 tts_generate of its prompt with the same settings
- * (rows never mix).  Opening slots discards an open tts_generate_begin generation. */
+ * (rows never mix).  Opening slots discards an open tts_generate_begin generation.
+ * Wide batches (n_slots, or tts_generate's batch, of 65..256): the decode step runs on the tile
+ * GEMMs, which sum K in canonical 1024-element chunks where the narrow steps sum in the decode
+ * stream's order.  Inside that regime a sequence's tokens depend only on its prompt, settings and
+ * key: not on its row, on what else is resident, or on whether it runs through tts_generate, the
+ * streaming calls or slots.  Against a narrow batch (or a batch-1 tts_generate) they are equal
+ * where the logit margins are decisive, not bit for bit on arbitrary weights: a different K order
+ * can round a bf16 logit the other way. */
 tts_status tts_slots_open(tts_engine* e, const tts_gen_params* p, int32_t n_slots, void* stream);
 tts_status tts_slots_add(tts_engine* e, int32_t slot, const int32_t* prompt_ids, int32_t prompt_len,
                          int32_t max_new_tokens);
@@ -181,7 +188,8 @@ tts_status tts_slots_add_seeded(tts_engine* e, int32_t slot, const int32_t* prom
  * Greedy and sampled requests share the batch.  Up to 16 rows (8 at hidden size 4096) with every
  * resident top_k <= 64 the step picks through the screened lm_head; a request with a larger top_k
  * moves the batch to the full lm_head (one recapture, until the batch is reopened), and batches of
- * 17..32 rows always take the full lm_head. */
+ * 17..256 rows always take the full lm_head (65..256 rows: the tile lm_head's per-row form, see
+ * tts_slots_open on wide batches). */
 tts_status tts_slots_open_per_request(tts_engine* e, const tts_gen_params* defaults, int32_t n_slots, void* stream);
 /* p NULL: the batch defaults.  seed NULL: a key derived from the batch seed as tts_slots_add does
  * (p->seed and p->max_length are ignored).  Only valid on a per-request batch: on a batch opened
@@ -231,7 +239,9 @@ tts_status tts_lm_last_timing(tts_engine* e, float* prefill_ms, float* decode_ms
  * rows), 9 its int8 screen alone, 10 the sampled step's screened head (temperature 0.8, top_k
  * 50: the screen's top-k mode, its exact recompute and the list sampler; 1..16 rows, 1..8 at
  * hidden 4096), 11 the full sampling head (the lm_head with its logits store + the dense
- * sampler).  rows = batch rows.
+ * sampler).  rows = batch rows, up to max_batch: above 64 rows every selector times what the
+ * wide step runs at that row count (0..3 the tile GEMMs; 4 and 11 the tile lm_head, or with
+ * TTS_WIDE_HEAD=0 the decode head in chunks; 5 the same row-generic attention).
  * Outputs: average ms per launch and the algorithmic HBM bytes one launch must move. */
 tts_status tts_lm_bench_kernel(tts_engine* e, int32_t which, int32_t rows, int32_t ctx,
                                int32_t iters, float* avg_ms, double* bytes);

@@ -41,6 +41,27 @@ tts_status tts_op_wgemm(const void* x, int32_t M, int32_t K, int32_t ldx, const 
 tts_status tts_op_pgemm(const void* x, int32_t M, int32_t K, const void* w_tiled, int32_t N, void* out,
                         int32_t ldo, void* resid, int32_t epi, void* stream);
 
+/* The lm_head with the pick's epilogue, alone, on caller-owned device buffers: for every row m of
+ * x [M][K] (bf16; RMSNorm'ed with normw / eps first when normw is not NULL) and column n of the
+ * tiled head (tts_op_retile, epi 0; N % 64 == 0, K % 128 == 0, M in 1..256)
+ *   v = bf16(x[m] . W[n]) as fp32;  bit n of seen[m] set: v = v < 0 ? v * penalty : v / penalty;
+ *   counts not NULL: v -= freq_penalty * counts[m][n];  n == eos_mask[m]: v = -inf
+ * (seen: [M][seen_stride] words, seen_stride >= N / 32; counts: uint16 [M][seen_stride * 32];
+ * eos_mask: int32 [M], -1 = none).  row_penalty / row_freq (both or neither; float [M], counts
+ * required): the per-row form, row m's penalties from the arrays instead of the scalars.
+ * Outputs: part_val / part_idx [M][1024], of which the first *nparts (host int) entries of a row
+ * are (maximum, lowest id holding it) of disjoint column sets that together cover every column —
+ * what finalize and the samplers reduce; logits_out (optional) fp32 [M][N], every v.
+ * form 0: the tile head of the 65..256-row decode step (lm_pgemm.hip head_tile_kernel): one
+ * launch, K summed in the canonical 1024-element chunks — bf16(sum) equals tts_op_pgemm's epi 0
+ * output bit for bit, at every M.  form 1: the decode head as the engine runs it up to 64 rows,
+ * in launches of 32 rows (the decode stream's K order; K % 256 == 0). */
+tts_status tts_op_head_pick(const void* x, int32_t M, int32_t K, const void* normw, float eps, const void* w_tiled,
+                            int32_t N, const uint32_t* seen, int32_t seen_stride, float penalty,
+                            const uint16_t* counts, float freq_penalty, const int32_t* eos_mask,
+                            const float* row_penalty, const float* row_freq, float* part_val, int32_t* part_idx,
+                            int32_t* nparts, float* logits_out, int32_t form, void* stream);
+
 /* Sampling head (GenerationMixin._sample with TemperatureLogitsWarper, TopKLogitsWarper,
  * TopPLogitsWarper; transformers logits_process.py:238,473,542): rows of processed fp32
  * logits [B][V] -> one drawn token per row (tokens, device int32 [B]) and, when `probs` is
@@ -79,23 +100,25 @@ tts_status tts_op_sample_rows(const float* scores, const int32_t* ids, const int
                               const int32_t* sample, const uint64_t* row_seed, int32_t step, const float* part_max,
                               const int32_t* part_idx, int32_t nparts, float* probs, int32_t* tokens, void* stream);
 
-/* Diagnostics, no GPU needed: the kernels one decode step over `rows` rows of a model of
+/* Diagnostics, no GPU needed: the kernels one decode step over `rows` rows (1..256) of a model of
  * config `cfg` would launch on a GPU of `num_cu` CUs — the engine's own step code run with
  * its launchers in a dry-run mode (nothing allocated or launched).  Writes the unique launches
  * in first-seen order, one per line (the weight-streaming GEMMs as
- * "wgemm_kernel<template arguments>"), NUL-terminated, into out[cap].  The build's spill gate
+ * "wgemm_kernel<template arguments>"; from 65 rows the tile GEMMs "pgemm_kernel<MW, NW, EPI>" and
+ * the tile lm_head "head_tile_kernel<MW, per-row>"), NUL-terminated, into out[cap].  The build's spill gate
  * (tests/test_kernel_resources.py) reads its hot instantiations from here. */
 tts_status tts_debug_step_plan(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, char* out, int32_t cap);
 /* ... of a sampled step (do_sample at temperature 0.8, top_p 1.0 and the given top_k in [1, 1024]):
  * the screened sampling head where it applies (head_screen_kernel<..., true> + sample_list_kernel),
- * else the full lm_head with its logits store + sample_kernel. */
+ * else the full lm_head with its logits store (65..256 rows: the tile lm_head) + sample_kernel. */
 tts_status tts_debug_step_plan_sampled(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t top_k,
                                        char* out, int32_t cap);
 
 /* ... of the per-request batch's step (tts_slots_open_per_request) whose largest admitted top_k is
  * max_top_k: the screen's per-row top-k variant (head_screen_kernel<MT, KT8, rows per wave + 8, false, true>) +
  * sample_list_rows_kernel where the rows and max_top_k fit the screen, else the full lm_head with
- * the per-row epilogue (wgemm_kernel<..., 4, ...>) + sample_rows_kernel. */
+ * the per-row epilogue (wgemm_kernel<..., 4, ...>; 65..256 rows: head_tile_kernel<MW, true>) +
+ * sample_rows_kernel. */
 tts_status tts_debug_step_plan_rows(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t max_top_k,
                                     char* out, int32_t cap);
 

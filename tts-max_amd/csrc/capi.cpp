@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <memory>
 #include <string>
 
@@ -443,6 +444,82 @@ tts_status tts_op_pgemm(const void* x, int32_t M, int32_t K, const void* w_tiled
     launch_pgemm(a, epi, device_cu_count(), s);
     HIP_CHECK(hipGetLastError());
     if (a.part) HIP_CHECK(hipFreeAsync(a.part, s));
+  });
+}
+
+tts_status tts_op_head_pick(const void* x, int32_t M, int32_t K, const void* normw, float eps, const void* w_tiled,
+                            int32_t N, const uint32_t* seen, int32_t seen_stride, float penalty,
+                            const uint16_t* counts, float freq_penalty, const int32_t* eos_mask,
+                            const float* row_penalty, const float* row_freq, float* part_val, int32_t* part_idx,
+                            int32_t* nparts, float* logits_out, int32_t form, void* stream) {
+  return guarded([&] {
+    TTS_REQUIRE(x && w_tiled && seen && eos_mask && part_val && part_idx && nparts, "null argument");
+    TTS_REQUIRE(form == 0 || form == 1, "form: 0 the tile head, 1 the decode head in chunks of 32");
+    TTS_REQUIRE(head_tile_supported(M, N, K), "M in [1, 256], N % 64 == 0, K % 128 == 0");
+    TTS_REQUIRE(form == 0 || wgemm_supported(std::min(M, 32), N, K, EPI_LOGITS), "unsupported decode head shape");
+    TTS_REQUIRE(seen_stride >= N / 32, "seen_stride below N / 32");
+    TTS_REQUIRE((row_penalty != nullptr) == (row_freq != nullptr), "the rows form takes both per-row arrays");
+    const bool rows = row_penalty != nullptr;
+    TTS_REQUIRE(!rows || counts, "the rows form needs counts");
+    hipStream_t s = (hipStream_t)stream;
+    const int ncu = device_cu_count();
+    const int epi = rows ? EPI_LOGITS_ROWS : EPI_LOGITS;
+    // the rows normalised once by the standalone pass, as the engine does from 17 rows on
+    bf16_t* xn = nullptr;
+    const bf16_t* xin = (const bf16_t*)x;
+    if (normw) {
+      HIP_CHECK(hipMallocAsync((void**)&xn, (size_t)M * K * 2, s));
+      launch_rmsnorm(xin, K, (const bf16_t*)normw, eps, xn, K, M, K, s);
+      xin = xn;
+    }
+    RowParams* par = nullptr;
+    if (rows) {  // the kernels read RowParams entries: a table from the two arrays
+      std::vector<float> pen(M), frq(M);
+      HIP_CHECK(hipMemcpyAsync(pen.data(), row_penalty, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(frq.data(), row_freq, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      std::vector<RowParams> tab(M);
+      for (int m = 0; m < M; ++m) {
+        TTS_REQUIRE(pen[m] > 0.f, "row penalties must be > 0");
+        tab[m] = RowParams{pen[m], frq[m], 1.f, 1.f, 1, -1, 0, 0};
+      }
+      HIP_CHECK(hipMallocAsync((void**)&par, (size_t)M * sizeof(RowParams), s));
+      HIP_CHECK(hipMemcpyAsync(par, tab.data(), (size_t)M * sizeof(RowParams), hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipStreamSynchronize(s));  // (tab is a local buffer)
+    }
+    if (form == 0) {
+      HeadTileArgs h;
+      h.g.x = xin; h.g.M = M; h.g.K = K; h.g.ldx = K;
+      h.g.w = (const bf16_t*)w_tiled; h.g.N = N;
+      h.seen = seen; h.seen_stride = seen_stride; h.penalty = penalty; h.eos_mask = eos_mask;
+      h.part_val = part_val; h.part_idx = part_idx; h.part_stride = LOGITS_MAX_PARTS;
+      h.logits_out = logits_out; h.ldl = N;
+      h.counts = counts; h.freq_penalty = freq_penalty; h.row_par = par;
+      launch_head_tile(h, rows, ncu, s);
+      *nparts = head_tile_nparts(N);
+    } else {
+      for (int r0 = 0; r0 < M; r0 += 32) {
+        const int m = std::min(32, M - r0);
+        const WgemmPlan p = plan_wgemm(m, N, K, epi, ncu);
+        TTS_REQUIRE(p.grid <= LOGITS_MAX_PARTS, "decode head grid above the partials' stride");
+        WgemmArgs a;
+        a.x = xin + (size_t)r0 * K; a.M = m; a.K = K; a.ldx = K;
+        a.w = (const bf16_t*)w_tiled; a.N = N;
+        a.seen = seen + (size_t)r0 * seen_stride; a.seen_stride = seen_stride; a.penalty = penalty;
+        a.eos_mask = eos_mask + r0;
+        a.part_val = part_val + (size_t)r0 * LOGITS_MAX_PARTS; a.part_idx = part_idx + (size_t)r0 * LOGITS_MAX_PARTS;
+        a.part_stride = LOGITS_MAX_PARTS;
+        if (logits_out) { a.logits_out = logits_out + (size_t)r0 * N; a.ldl = N; }
+        if (counts) a.counts = counts + (size_t)r0 * seen_stride * 32;
+        a.freq_penalty = freq_penalty;
+        if (par) a.row_par = par + r0;
+        launch_wgemm(a, p, epi, false, s);
+        *nparts = p.grid;
+      }
+    }
+    HIP_CHECK(hipGetLastError());
+    if (par) HIP_CHECK(hipFreeAsync(par, s));
+    if (xn) HIP_CHECK(hipFreeAsync(xn, s));
   });
 }
 

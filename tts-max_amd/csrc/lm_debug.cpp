@@ -92,7 +92,8 @@ void lm_bench_kernel(Engine* e, int which, int rows, int ctx, int iters, float* 
         b = 2.0 * HID * FF + act_rw * (FF + 2 * HID);
         break;
       case 4:
-        X.lm_head_pick(e->w.x.as<bf16_t>(), rows, ex);
+        X.pending_norm = nullptr;
+        X.lm_head_pick(e->w.x.as<bf16_t>(), rows, ex, EPI_LOGITS, true);  // (> 64 rows: the wide step's head)
         b = 2.0 * V * HID + act_rw * HID + 2.0 * HID + rows * (V / 8.0);
         break;
       case 5:
@@ -126,8 +127,9 @@ void lm_bench_kernel(Engine* e, int which, int rows, int ctx, int iters, float* 
           // (+ the recomputed units' bf16 tiles and the candidate lists, not counted)
           b = (double)V * HID + 16.0 * V + act_rw * HID + rows * (V / 8.0);
         } else {
-          X.lm_head_pick(e->w.x.as<bf16_t>(), rows, sx);
-          SampleArgs sa = X.sample_args(st, sampled, false, plan_wgemm(rows, V, HID, EPI_LOGITS, e->num_cu).grid);
+          X.pending_norm = nullptr;
+          X.lm_head_pick(e->w.x.as<bf16_t>(), rows, sx, EPI_LOGITS, true);
+          SampleArgs sa = X.sample_args(st, sampled, false, X.head_parts(rows, EPI_LOGITS, true));
           sa.out_part_val = nullptr; sa.out_part_idx = nullptr;  // (not the partials: the next launch's
           sa.tokens = e->w.row_idx.as<int>();                    //  bound reads them)
           launch_sample(sa, rows, s);

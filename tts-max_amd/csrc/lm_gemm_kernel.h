@@ -10,6 +10,7 @@
 #include "hip_common.h"
 #include "lm_kernels.h"
 #include "lm_attn_core.h"
+#include "lm_logit_epilogue.h"
 
 namespace tts {
 
@@ -310,11 +311,6 @@ TTS_DEV void fused_oproj_rows(const WgemmArgs& a, bf16_t* xs, float* red, int wa
 // of KU tiles (KU KiB), double-buffered, and the stream never stops: the first stage is
 // issued before the A-operand prologue (RMSNorm / attention combine), and the last stage
 // of a unit prefetches the first stage of the wave's next unit.
-
-// Better (value, index): larger value wins, lower index on ties (torch.argmax semantics).
-TTS_DEV void argmax_merge(float& v, int& i, float v2, int i2) {
-  if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-}
 
 constexpr int A_GLOBAL = 0, A_LDS = 1;
 
@@ -864,19 +860,8 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
             const float up = rbf(acc[NG - 1][mt][r]);
             a.out[(size_t)m * a.ldo + n] = f2bf(rbf(silu_f(gt)) * up);
           } else if constexpr (LOGITS) {
-            float v = rbf(acc[0][mt][r]);  // logits are materialised in bf16, then .float()
-            const uint32_t bits = seen_cur[mt][r];
-            if constexpr (EPI == EPI_LOGITS_ROWS) {
-              // the row's own penalties (one 8-byte load beside the counts'); freq 0 subtracts an exact zero
-              const float2 pf = *(const float2*)(a.row_par + m);
-              if ((bits >> (n & 31)) & 1u) v = (v < 0.f) ? v * pf.x : v / pf.x;
-              v -= pf.y * (float)a.counts[(size_t)m * a.seen_stride * 32 + n];
-            } else {
-              if ((bits >> (n & 31)) & 1u) v = (v < 0.f) ? v * a.penalty : v / a.penalty;
-              if (a.counts) v -= a.freq_penalty * (float)a.counts[(size_t)m * a.seen_stride * 32 + n];
-            }
-            if (n == eosr[mt][r]) v = -INFINITY;
-            if (a.logits_out) a.logits_out[(size_t)m * a.ldl + n] = v;
+            // (the arithmetic: lm_logit_epilogue.h, shared with the tile head)
+            const float v = logit_epilogue<EPI == EPI_LOGITS_ROWS>(a, acc[0][mt][r], seen_cur[mt][r], m, n, eosr[mt][r]);
             argmax_merge(best_v[mt][r], best_i[mt][r], v, n);
           }
         }

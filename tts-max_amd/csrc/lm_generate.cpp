@@ -35,7 +35,7 @@ static void ensure_step_graph(Engine* e, int B, const StepState& st, const tts_g
   Ctx Y(e, cs);
   Y.layers(B, W.row_slot.as<int>(), st.pos, true);
   if (per_row) Y.head_and_pick_rows(W.x.as<bf16_t>(), B, st, dense, max_top_k);
-  else Y.head_and_pick(W.x.as<bf16_t>(), B, st, gp);
+  else Y.head_and_pick(W.x.as<bf16_t>(), B, st, gp, true);
   HIP_CHECK(hipStreamEndCapture(cs, &g));
   HIP_CHECK(hipGraphInstantiate(&W.graph, g, nullptr, nullptr, 0));
   HIP_CHECK(hipGraphDestroy(g));

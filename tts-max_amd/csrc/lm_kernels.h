@@ -286,6 +286,34 @@ bool pgemm_supported(int M, int N, int K, int epi);
 size_t pgemm_part_bytes(int M, int N, int K);  // the one-chunk form's partials of an M x N x K GEMM
 bool launch_pgemm(const PgemmArgs& a, int epi, int num_cu, hipStream_t s);  // true: xn written
 
+// ---- tile lm_head (lm_pgemm.hip, head_tile_kernel): the lm_head over 65..256 decode rows with the
+// pick's epilogue (EPI_LOGITS / EPI_LOGITS_ROWS, lm_logit_epilogue.h) on the prefill GEMM's tile
+// schedule, so the head streams once for every row.  Column blocks are 64 wide; a workgroup owns
+// an m-block and a group of consecutive column blocks (all of K each, canonical chunks: the fp32
+// sums of pgemm_kernel<.., EPI_STORE>) and carries each row's running argmax over the group: row
+// m ends with head_tile_nparts(N) partials (value, id), partial g covering the columns of group g.
+struct HeadTileArgs {
+  PgemmArgs g;  // x (normalised rows), M, K, ldx, w (the tiled head), N; the rest filled in by the launch
+  // the epilogue's operands, named as WgemmArgs names them (logit_epilogue reads either)
+  const uint32_t* seen = nullptr;  // [M][seen_stride]
+  int seen_stride = 0;
+  float penalty = 1.f;
+  const int* eos_mask = nullptr;  // [M]
+  float* part_val = nullptr;      // [M][part_stride]
+  int* part_idx = nullptr;
+  int part_stride = 0;
+  float* logits_out = nullptr;  // optional: the processed fp32 logits [M][ldl]
+  int ldl = 0;
+  const uint16_t* counts = nullptr;  // [M][seen_stride*32] or nullptr
+  float freq_penalty = 0.f;
+  const RowParams* row_par = nullptr;  // the per-row form: [M] (counts set)
+  int cb = 1, groups = 1;              // column blocks per group, groups (filled in by the launch)
+};
+constexpr int kHeadTileMaxRows = 256;
+bool head_tile_supported(int M, int N, int K);  // 1 <= M <= 256, N % 64 == 0, K % 128 == 0
+int head_tile_nparts(int N);                    // argmax partials per row (<= LOGITS_MAX_PARTS)
+void launch_head_tile(const HeadTileArgs& a, bool per_row, int num_cu, hipStream_t s);
+
 // ---- elementwise / small kernels (lm_ops.hip)
 void launch_rmsnorm(const bf16_t* x, int ldx, const bf16_t* w, float eps, bf16_t* y, int ldy,
                     int M, int K, hipStream_t s);

@@ -109,7 +109,7 @@ size_t kpart_bytes(const tts_lm_config& c) {
 // prefill GEMMs of <= kPgemmSplitRows rows may take one canonical K chunk per workgroup
 // (lm_pgemm.hip): fp32 partials [chunks][rows][N] of the largest of the layer's four GEMMs
 static constexpr int kPgemmSplitRows = 256;
-static size_t ppart_bytes(const tts_lm_config& c) {
+size_t ppart_bytes(const tts_lm_config& c) {
   const int H = c.hidden_size, HD = c.num_heads * c.head_dim, FF = c.intermediate_size;
   const int QKV = (c.num_heads + 2 * c.num_kv_heads) * c.head_dim;
   return std::max(std::max(pgemm_part_bytes(kPgemmSplitRows, QKV, H), pgemm_part_bytes(kPgemmSplitRows, H, HD)),
@@ -138,7 +138,7 @@ void lm_load(Engine* e, const tts_lm_config* cfgp, const tts_tensor_desc* t, int
   TTS_REQUIRE((double)c.vocab_size * c.hidden_size * 2 < 4.0e9 &&
                   (double)2 * c.intermediate_size * c.hidden_size * 2 < 4.0e9,
               "a weight matrix of 4 GB or more is not supported");
-  TTS_REQUIRE(c.max_batch >= 1 && c.max_batch <= 64, "max_batch must be in [1, 64]");
+  TTS_REQUIRE(c.max_batch >= 1 && c.max_batch <= kHeadTileMaxRows, "max_batch must be in [1, 256]");
   TTS_REQUIRE(c.max_seq_len >= 16, "max_seq_len too small");
   TensorMap tm;
   for (int i = 0; i < n; ++i) tm.m[t[i].name] = &t[i];

@@ -34,6 +34,11 @@ static bool use_kslice32() { static const bool v = env_on("TTS_KSLICE32"); retur
 // workgroups after the attention's): default on; TTS_FUSED_OPROJ_ROWS=0 keeps the launch
 static bool use_fused_oproj_rows() { static const bool v = env_on("TTS_FUSED_OPROJ_ROWS"); return v; }
 
+// The lm_head of a 65..256-row decode step as one tile launch (head_tile_kernel, lm_pgemm.hip):
+// default on; TTS_WIDE_HEAD=0 runs it as the 32-row decode head in chunks (the head streamed once
+// per chunk; the decode stream's K order instead of the canonical chunks)
+static bool use_wide_head() { static const bool v = env_on("TTS_WIDE_HEAD"); return v; }
+
 StepState step_state_row(const StepState& st, int slot) {
   StepState one = st;
   one.tokens += slot; one.pos += slot; one.gen_count += slot; one.limit += slot;
@@ -55,11 +60,28 @@ bool Ctx::norm_once_ok(int rows) const {
 
 // out = epi(x . W^T) over g.rows rows (chunked by 64), RMSNorm prologue if g.normw
 bool Ctx::gemm(const Gemm& g) {
-  const auto [x, rows, K, W, N, epi, out, ldo, normw, resid, logit_extra, next_norm, defer_combine] = g;
+  const auto [x, rows, K, W, N, epi, out, ldo, normw, resid, logit_extra, next_norm, defer_combine, tile_head] = g;
   bool part_left = false;
   const bf16_t* ready = pending_norm;
   if (resid) pending_norm = nullptr;  // the residual stream changes below
-  if (rows > kPrefillChunk && x && pgemm_supported(rows, N, K, epi)) {
+  const bool have_x = x || dry_launches();  // (a dry run has no buffers)
+  if (tile_head && rows > kPrefillChunk && have_x && logit_extra && use_wide_head() && head_tile_supported(rows, N, K)) {
+    // the wide decode step's lm_head: every row in one tile launch with the pick's epilogue
+    TTS_REQUIRE(normw != nullptr, "the tile lm_head reads normalised rows");
+    if (!(normw == ready && x == w.x.as<bf16_t>()))
+      launch_rmsnorm(x, K, normw, c.rms_norm_eps, w.xn.as<bf16_t>(), K, rows, K, s);
+    const WgemmArgs& ex = *logit_extra;
+    HeadTileArgs h;
+    h.g.x = w.xn.as<bf16_t>(); h.g.M = rows; h.g.K = K; h.g.ldx = K;
+    h.g.w = W; h.g.N = N;
+    h.seen = ex.seen; h.seen_stride = ex.seen_stride; h.penalty = ex.penalty; h.eos_mask = ex.eos_mask;
+    h.part_val = ex.part_val; h.part_idx = ex.part_idx; h.part_stride = ex.part_stride;
+    h.logits_out = ex.logits_out; h.ldl = ex.ldl;
+    h.counts = ex.counts; h.freq_penalty = ex.freq_penalty; h.row_par = ex.row_par;
+    launch_head_tile(h, epi == EPI_LOGITS_ROWS, e->num_cu, s);
+    return false;
+  }
+  if (rows > kPrefillChunk && have_x && pgemm_supported(rows, N, K, epi)) {
     // prefill: every prompt row of the batch in one LDS-staged MFMA launch
     const bf16_t* xin = x;
     if (normw) {
@@ -81,7 +103,8 @@ bool Ctx::gemm(const Gemm& g) {
   }
   // decode GEMV launches hold at most 32 rows (two m-tiles: the A rows fit LDS); 33..64
   // rows run as two launches (the weights stream twice, still far cheaper than A rows
-  // read from global memory)
+  // read from global memory); so does the lm_head of more rows where the tile head does not run
+  // (the first token of a 65..256-row generate; TTS_WIDE_HEAD=0)
   const int chunk = rows > 32 ? 32 : kPrefillChunk;
   for (int r0 = 0; r0 < rows; r0 += chunk) {
     const int m = std::min(chunk, rows - r0);
@@ -326,7 +349,15 @@ SampleArgs Ctx::sample_args(const StepState& st, const tts_gen_params& gp, bool 
   return sa;
 }
 
-void Ctx::head_and_pick(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp) {
+// The argmax partials a full-head launch over B rows leaves per row: the tile head's column groups
+// (the wide step), else the decode head's workgroups
+int Ctx::head_parts(int B, int epi, bool step) const {
+  if (step && B > kPrefillChunk && use_wide_head() && head_tile_supported(B, c.vocab_size, c.hidden_size))
+    return head_tile_nparts(c.vocab_size);
+  return plan_wgemm(std::min(B, kPrefillChunk), c.vocab_size, c.hidden_size, epi, e->num_cu).grid;
+}
+
+void Ctx::head_and_pick(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp, bool step) {
   // greedy pick through the int8 screen + exact recheck (lm_head_screen.hip): the same ids as
   // the full lm_head launch below
   if (!gp.do_sample && M.head_grid && head_screen_supported(B, c.hidden_size, c.vocab_size)) {
@@ -340,9 +371,9 @@ void Ctx::head_and_pick(const bf16_t* xin, int B, const StepState& st, const tts
     finalize(1, B, st);
     return;
   }
-  TTS_REQUIRE(B <= kPrefillChunk, "batch larger than one GEMM chunk");
-  int nparts = plan_wgemm(B, c.vocab_size, c.hidden_size, EPI_LOGITS, e->num_cu).grid;
-  lm_head_pick(xin, B, head_epilogue_args(st, gp));
+  TTS_REQUIRE(B <= kHeadTileMaxRows, "batch larger than the widest step");
+  int nparts = head_parts(B, EPI_LOGITS, step);
+  lm_head_pick(xin, B, head_epilogue_args(st, gp), EPI_LOGITS, step);
   if (gp.do_sample) {
     launch_sample(sample_args(st, gp, false, nparts), B, s);
     nparts = 1;
@@ -368,11 +399,11 @@ void Ctx::head_and_pick_rows(const bf16_t* xin, int B, const StepState& st, bool
     finalize(1, B, st);
     return;
   }
-  TTS_REQUIRE(B <= kPrefillChunk, "batch larger than one GEMM chunk");
-  const int nparts = plan_wgemm(B, c.vocab_size, c.hidden_size, EPI_LOGITS_ROWS, e->num_cu).grid;
+  TTS_REQUIRE(B <= kHeadTileMaxRows, "batch larger than the widest step");
+  const int nparts = head_parts(B, EPI_LOGITS_ROWS, true);  // (the per-row pick is the captured step's only)
   WgemmArgs ex = head_epilogue_args(st, gp);
   ex.row_par = st.par;
-  lm_head_pick(xin, B, ex, EPI_LOGITS_ROWS);
+  lm_head_pick(xin, B, ex, EPI_LOGITS_ROWS, true);
   SampleArgs sa = sample_args(st, gp, false, nparts);
   sa.part_idx = w.lpart_i.as<int>();  // (a greedy row's argmax partials)
   sample_rows_from_table(sa, st.par);
@@ -489,7 +520,7 @@ void Ctx::prefill_all(const int32_t* ids, const std::vector<int>& start, const s
 std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k, bool per_row) {
   TTS_REQUIRE(c.head_dim == 64 || c.head_dim == 128, "head_dim must be 64 or 128");
   TTS_REQUIRE(c.num_heads == 4 * c.num_kv_heads && c.num_layers >= 1, "bad config");
-  TTS_REQUIRE(rows >= 1 && rows <= 64 && num_cu >= 1, "rows in [1, 64], num_cu >= 1");
+  TTS_REQUIRE(rows >= 1 && rows <= kHeadTileMaxRows && num_cu >= 1, "rows in [1, 256], num_cu >= 1");
   Engine e;  // (no HIP call: no stream, no buffer)
   e.num_cu = num_cu;
   e.lm.cfg = c;
@@ -506,7 +537,8 @@ std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k
   e.lm.lm_head = next();
   e.lm.head_grid = head_screen_grid(c, num_cu);
   e.w.cap_batch = e.lm.cfg.max_batch;
-  e.w.kpart.bytes = kpart_bytes(c);  // (the size the plan checks; never dereferenced)
+  e.w.kpart.bytes = kpart_bytes(c);  // (the sizes the plan checks; never dereferenced)
+  e.w.ppart.bytes = ppart_bytes(c);
   std::vector<std::string> rec;
   dry_launches() = &rec;
   try {
@@ -523,15 +555,17 @@ std::string lm_step_plan(const tts_lm_config& c, int rows, int num_cu, int top_k
       st.counts = (uint16_t*)next();
       X.head_and_pick_rows(nullptr, rows, st, !X.rows_screen_ok(rows, top_k), top_k);
     } else {
-      X.head_and_pick(nullptr, rows, st, gp);
+      X.head_and_pick(nullptr, rows, st, gp, true);
     }
   } catch (...) {
     dry_launches() = nullptr;
     e.w.kpart.bytes = 0;
+    e.w.ppart.bytes = 0;
     throw;
   }
   dry_launches() = nullptr;
   e.w.kpart.bytes = 0;
+  e.w.ppart.bytes = 0;
   std::string out;
   std::vector<std::string> seen;
   for (const std::string& r : rec)

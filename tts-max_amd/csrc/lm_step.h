@@ -11,10 +11,11 @@
 
 namespace tts {
 
-constexpr int kPrefillChunk = 64;   // rows per GEMM launch (MFMA A-tiles of 16)
+constexpr int kPrefillChunk = 64;   // rows per decode GEMM launch set (MFMA A-tiles of 16); more rows: the tile GEMMs
 constexpr int kMaxPrefillRows = 8192;
 
 size_t kpart_bytes(const tts_lm_config& c);                // lm_load.cpp: LmWork::kpart's size
+size_t ppart_bytes(const tts_lm_config& c);                // lm_load.cpp: LmWork::ppart's size
 int head_screen_grid(const tts_lm_config& c, int num_cu);  // lm_load.cpp: the int8 screen's grid (0: no screen)
 bool head_screen_check();                                  // lm_step.cpp: TTS_HEAD_SCREEN_CHECK
 unsigned long long* stamp_buf();                           // lm_debug.cpp: null but in the stamps build
@@ -72,9 +73,10 @@ struct Ctx {
     gemm(g);
   }
   // lm_head over RMSNorm(x, final norm): the processing epilogue + argmax partials, or plain logits
-  void lm_head_pick(const bf16_t* x, int rows, const WgemmArgs& epilogue, int epi = EPI_LOGITS) {
+  // (tile_head: more than kPrefillChunk rows may run as the tile head, the wide decode step's form)
+  void lm_head_pick(const bf16_t* x, int rows, const WgemmArgs& epilogue, int epi = EPI_LOGITS, bool tile_head = false) {
     Gemm g{x, rows, c.hidden_size, M.lm_head, c.vocab_size, epi};
-    g.normw = M.final_norm; g.extra = &epilogue;
+    g.normw = M.final_norm; g.extra = &epilogue; g.tile_head = tile_head;
     gemm(g);
   }
   void lm_head_logits(const bf16_t* x, int rows, bf16_t* out) {  // out: bf16 [rows][V]
@@ -94,7 +96,10 @@ struct Ctx {
   WgemmArgs head_epilogue_args(const StepState& st, const tts_gen_params& gp);  // lm_head_pick's
   // the sampler's: over the dense logits (nparts workgroup maxima a row) or the screen's lists
   SampleArgs sample_args(const StepState& st, const tts_gen_params& gp, bool lists, int nparts = 0);
-  void head_and_pick(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp);
+  // step: the decode step's pick (65..256 rows: the tile head); else a first token from prefilled
+  // rows, which takes the decode head's K order at every B, as a slot admission's batch of 1 does
+  void head_and_pick(const bf16_t* xin, int B, const StepState& st, const tts_gen_params& gp, bool step = false);
+  int head_parts(int B, int epi, bool step) const;
   // the per-request batch's pick (st.par, st.counts set): the screen's per-row top-k form + the
   // per-row list sampler where the rows and max_top_k fit it and !dense, else the per-row full head
   // + the per-row dense sampler
@@ -131,6 +136,7 @@ struct Ctx {
     const WgemmArgs* extra = nullptr;   // the lm_head epilogue's, or the fused attention's, operands
     const bf16_t* next_norm = nullptr;  // EPI_RESID: the combine may normalise into w.xn
     bool defer_combine = false;         // EPI_STORE, 17..32 rows: partials may stay in w.kpart
+    bool tile_head = false;             // EPI_LOGITS*, > kPrefillChunk rows: the tile head (TTS_WIDE_HEAD)
   };
   bool gemm(const Gemm& g);  // true: the partials were left in w.kpart (defer_combine)
   bool norm_once_ok(int rows) const;

@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = (
     "tts_op_gemm_f32",
     "tts_op_attn_prefill",
     "tts_op_attn_decode",
+    "tts_op_head_pick",
 )
 
 
@@ -198,6 +199,7 @@ def load_library() -> ctypes.CDLL:
         "tts_op_retile": (I32, [P, P, I32, I32, I32, P]),
         "tts_op_wgemm": (I32, [P, I32, I32, I32, P, I32, P, F32, P, I32, P, I32, P]),
         "tts_op_pgemm": (I32, [P, I32, I32, P, I32, P, I32, P, I32, P]),
+        "tts_op_head_pick": (I32, [P, I32, I32, P, F32, P, I32, P, I32, F32, P, F32, P, P, P, P, P, pi32, P, I32, P]),
         "tts_op_sample": (I32, [P, I32, I32, F32, I32, F32, ctypes.c_uint64, I32, P, I32, P, P, P]),
         "tts_op_sample_list": (I32, [P, P, P, I32, I32, I32, F32, I32, F32, ctypes.c_uint64, I32, P, P, P]),
         "tts_op_sample_rows": (I32, [P, P, P, I32, I32, I32, P, P, P, P, P, I32, P, P, I32, P, P, P]),

@@ -9,7 +9,9 @@ backed by the engine's slot API (``tts_slots_*``):
 * ``ContinuousBatcher`` — S persistent decode rows; queued requests are admitted into free
   rows between decode chunks and retired when they stop (EOS / max_tokens), so long and short
   utterances share the GPU without padding or waiting for the longest one.  Every request's
-  tokens equal a batch-1 generate of its prompt with the batcher's settings (rows never mix;
+  tokens equal a batch-1 generate of its prompt with the batcher's settings (up to 256 rows; above
+  64 the step sums K in another order and the equality holds where margins are decisive, see
+  tts_slots_open in include/tts_mi355x.h) (rows never mix;
   tests/test_gpu_serving.py).
 * ``LLM`` — vLLM-shaped facade: ``generate(prompt_token_ids=list | list[list], sampling_params)``.
 * ``create_app`` — a FastAPI app (``POST /generate``: ``{"prompt_token_ids": [...],
@@ -28,6 +30,7 @@ request's tokens still equal a uniform batcher's with that request's settings an
 
 from __future__ import annotations
 
+import collections
 import ctypes
 import dataclasses
 import threading
@@ -105,7 +108,7 @@ class ContinuousBatcher:
                                  do_sample=1 if do_sample else 0, repetition_penalty=repetition_penalty,
                                  temperature=temperature, top_p=top_p, top_k=top_k, seed=seed or 0,
                                  frequency_penalty=frequency_penalty)
-        self._queue: list[_Req] = []
+        self._queue: collections.deque[_Req] = collections.deque()  # (O(1) admission at any slot count)
         self._slot_req: list[_Req | None] = [None] * n_slots
         self._lock = threading.Lock()
         self._wake = threading.Event()
@@ -165,9 +168,9 @@ class ContinuousBatcher:
         (no future is left pending), and later submissions fail at once."""
         self.error = ex
         with self._lock:
-            reqs = [r for r in self._slot_req if r is not None] + self._queue
+            reqs = [r for r in self._slot_req if r is not None] + list(self._queue)
             self._slot_req = [None] * self.S
-            self._queue = []
+            self._queue.clear()
         for r in reqs:
             if not r.future.done():
                 r.future.set_exception(ex)
@@ -195,7 +198,7 @@ class ContinuousBatcher:
         with self._lock:
             for s in range(self.S):
                 if self._slot_req[s] is None and self._queue:
-                    r = self._queue.pop(0)
+                    r = self._queue.popleft()
                     arr = np.ascontiguousarray(np.asarray(r.prompt, dtype=np.int32))
                     try:
                         if r.settings is not None:
