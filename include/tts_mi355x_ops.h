@@ -108,6 +108,11 @@ tts_status tts_op_sample_rows(const float* scores, const int32_t* ids, const int
  * the tile lm_head "head_tile_kernel<MW, per-row>"), NUL-terminated, into out[cap].  The build's spill gate
  * (tests/test_kernel_resources.py) reads its hot instantiations from here. */
 tts_status tts_debug_step_plan(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, char* out, int32_t cap);
+/* Diagnostics, no GPU needed: the decode GEMM's plan for an M x N x K launch with epilogue epi
+ * (0 store, 1 residual, 2 SwiGLU, 3 / 4 lm_head) on a GPU of num_cu CUs, as out[8] = {layout
+ * units, units per layout round (ur), launch grid, K chunks (kc), csplit, K-sliced, A rows in
+ * LDS, launch shape index}: units > ur with units % ur != 0 is a partial last round. */
+tts_status tts_debug_wgemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t num_cu, int32_t* out);
 /* ... of a sampled step (do_sample at temperature 0.8, top_p 1.0 and the given top_k in [1, 1024]):
  * the screened sampling head where it applies (head_screen_kernel<..., true> + sample_list_kernel),
  * else the full lm_head with its logits store (65..256 rows: the tile lm_head) + sample_kernel. */

@@ -15,7 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tts-max_amd"))
 from tts_amd import _lib, configs  # noqa: E402
 
-_lib.LIB_PATH = os.path.join(ROOT, "tts-max_amd", "tts_amd", "libtts_mi355x_stamps.so")
+# (TTS_LIB_PATH: another stamps build, e.g. a parent commit's for a before / after)
+_lib.LIB_PATH = os.environ.get("TTS_LIB_PATH") or os.path.join(ROOT, "tts-max_amd", "tts_amd", "libtts_mi355x_stamps.so")
 lib = _lib.load_library()
 from tts_amd.speechlm import MI355XSpeechLM  # noqa: E402
 
@@ -52,6 +53,17 @@ for k in ("qkv", "o_proj", "gate_up", "down", "attention", "qkv_attn", "qkv_attn
     us = (st - t0) / 100.0
     us[st == 0] = np.nan
     print(f"{k} ctx={ctx} rows={rows}: {len(st)} workgroups (min/median/max us from first entry)")
+
+    def prologue(g):
+        """GEMM workgroups: per workgroup, from its own first instruction (stamp 25, read before the
+        argument fetch) to stamp 0 (arguments there), stamp 26 (primed weight stages issued) and
+        stamp 1 (A in LDS) — builds without the first-instruction stamp print nothing."""
+        if np.all(np.isnan(g[:, 25])):
+            return
+        d = g - g[:, 25:26]
+        print(f"  from the first instruction: arguments {q(d[:, 0])}  primed stages issued {q(d[:, 26])}  "
+              f"A landed (prologue done) {q(d[:, 1])}")
+
     if k in ("qkv_attn", "qkv_attn_oproj"):
         # grid order: projection | attention | o_proj workgroups
         na = rows * arch.num_kv_heads
@@ -65,11 +77,13 @@ for k in ("qkv", "o_proj", "gate_up", "down", "attention", "qkv_attn", "qkv_attn
             print(f"  o_proj      entry {q(op[:, 0])}  row 0 granules {q(op[:, 1])}  all rows {q(op[:, 2])}  done {q(op[:, 3])}")
 
         print(f"  projection  entry {q(proj[:, 0])}  prologue {q(proj[:, 1])}  streamed {q(proj[:, 2])}  epilogue {q(proj[:, 3])}")
+        prologue(proj)
         print(f"  attention   entry {q(cons[:, 0])}  granules {q(cons[:, 1])}  rope {q(cons[:, 2])}  max {q(cons[:, 5])}  pv {q(cons[:, 6])}  attended {q(cons[:, 3])}")
     elif k == "attention":
         print(f"  entry {q(us[:, 0])}  rope {q(us[:, 2])}  attended {q(us[:, 3])}")
     else:
         print(f"  entry {q(us[:, 0])}  prologue {q(us[:, 1])}  streamed {q(us[:, 2])}  epilogue {q(us[:, 3])}")
+        prologue(us)
         if not np.all(np.isnan(us[:, 6])):
             print(f"  A rows landed (LDS-DMA) {q(us[:, 6])}")
         if not np.all(np.isnan(us[:, 7])):

@@ -270,6 +270,22 @@ tts_status tts_debug_step_plan(const tts_lm_config* cfg, int32_t rows, int32_t n
   });
 }
 
+tts_status tts_debug_wgemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t num_cu, int32_t* out) {
+  return guarded([&] {
+    TTS_REQUIRE(out && num_cu > 0, "null argument");
+    TTS_REQUIRE(epi >= EPI_STORE && epi <= EPI_LOGITS_ROWS && wgemm_supported(M, N, K, epi), "unsupported GEMM shape");
+    const WgemmPlan p = plan_wgemm(M, N, K, epi, num_cu);
+    out[0] = (N / 16) / p.sp.ng;  // layout units
+    out[1] = p.sp.ur();           // units per round of the layout
+    out[2] = p.grid;
+    out[3] = p.sp.kc;
+    out[4] = p.csplit;
+    out[5] = p.sliced ? 1 : 0;
+    out[6] = p.a_lds ? 1 : 0;
+    out[7] = p.cfg;
+  });
+}
+
 tts_status tts_debug_step_plan_sampled(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t top_k,
                                        char* out, int32_t cap) {
   return guarded([&] {

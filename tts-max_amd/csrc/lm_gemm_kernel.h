@@ -71,7 +71,7 @@ TTS_DEV void fattn_consumer(const WgemmArgs& wa, char* smem, int b) {
   float* red = (float*)(vnew + D);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int row = b / a.KVH, kvh = b % a.KVH;
+  const int row = (int)fastdiv((uint32_t)b, wa.kvh_div), kvh = b - row * a.KVH;
   const int slot = a.row_slot[row], pos = a.row_pos[row], ctx = pos + 1;
   const size_t kvbase = ((size_t)slot * a.KVH + kvh) * a.max_seq * D;
   const bf16_t* kc = a.kcache + kvbase;
@@ -217,9 +217,9 @@ TTS_DEV void fused_oproj_rows(const WgemmArgs& a, bf16_t* xs, float* red, int wa
   TTS_STAMP(stp, 0);
   const int kpart = wave % KSPLIT;
   const int nr = min(a.fo_ur, a.fo_units);
-  const int KTc = (HD >> 5) / a.fo_kc, kt_pc = KTc / KSPLIT, Sc = kt_pc / KU;
+  const int Sc = a.fo_Sc, kt_pc = Sc * KU, KTc = kt_pc * KSPLIT;  // (the host's quotients, wgemm_derive)
   auto ktile = [&](int st, int kk) {  // absolute k-tile of stage st, tile kk of this wave
-    const int ch = st / Sc;
+    const int ch = (int)fastdiv((uint32_t)st, a.fo_sc_div);
     return ch * KTc + kpart * kt_pc + (st - ch * Sc) * KU + kk;
   };
   u32x4_t wr[R][KU];
@@ -331,13 +331,31 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
   // register-staged instantiation keeps the consumer's registers out)
   constexpr bool FATT = EPI == EPI_STORE && ASRC == A_LDS && WAVES == DEC_NW && KSW == KSPLIT && MT_MAX == 1 &&
                         ((EARLY && !FROWS && wgemm_fattn_d(KU) == 64) || (!EARLY && FROWS));
+#ifdef TTS_STAMPS
+  const unsigned long long t_first = __builtin_amdgcn_s_memrealtime();  // (the kernel's first instruction)
+#endif
+  // The two argument lines of the prologue (WgemmArgs) are fetched here, in one batch ahead of
+  // the role branch: the empty asm needs every field in a scalar register at this point, so
+  // the compiler cannot sink a fetch into the path that first uses it (each such later batch
+  // was a wait of its own, on a line the earlier ones had not touched).
+  asm volatile("" ::"s"(a.x), "s"(a.w), "s"(a.normw), "s"(a.resid), "s"(a.stamps), "s"(a.M), "s"(a.K), "s"(a.ldx),
+               "s"(a.N), "s"(a.ldo), "s"(a.ur));
+  asm volatile("" ::"s"(a.fattn_wgs), "s"(a.fo_units), "s"(a.csplit), "s"(a.sliced), "s"(a.diag), "s"(a.KT), "s"(a.Sc),
+               "s"(a.S), "s"(a.units), "s"(a.nproj), "s"(a.ur_div.mul), "s"(a.ur_div.shift), "s"(a.kch_div.mul),
+               "s"(a.kch_div.shift), "s"(a.sc_div.mul), "s"(a.sc_div.shift));
   // fused launch (a.fattn_wgs): the grid's projection workgroups, then the attention
   // workgroups, then (fo_units > 0) the o_proj workgroups (WgemmArgs::fattn_wgs)
-  const int fo_wgs = (FATT && a.fattn_wgs) ? a.fo_units : 0;
-  const int nproj = (int)gridDim.x - (FATT ? a.fattn_wgs : 0) - fo_wgs;
+  // (FROWS, the 2..16-row fused launch, keeps the role dispatch it has always been compiled
+  // with — the grid's size from the dispatch, an outer test of a.fattn_wgs — because its
+  // attention role sits at the register limit and the allocation of its K / V loop moves by
+  // two VGPRs with the shape of this dispatch, tests/test_attn_chain_resources.py; its
+  // projection does not head the step's chain as the one-row launch's does)
+  const int nproj = FROWS ? (int)gridDim.x - a.fattn_wgs - (a.fattn_wgs ? a.fo_units : 0) : a.nproj;
   if constexpr (FATT) {
-    if (a.fattn_wgs) {
-      const int cb = (int)blockIdx.x - nproj;
+    // (one row: one test on the projection's path, and none of the other roles' argument
+    // fetches on it: without fused roles nproj is the whole grid)
+    const int cb = (int)blockIdx.x - nproj;
+    if (FROWS ? a.fattn_wgs != 0 : cb >= 0) {
       if (cb >= 0 && cb < a.fattn_wgs) {
         fattn_consumer<NT, wgemm_fattn_d(KU)>(a, smem, cb);
         return;
@@ -361,6 +379,9 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
   const int bx = (int)blockIdx.x;  // (the projection workgroups come first in a fused launch's grid)
   unsigned long long* stp = a.stamps ? a.stamps + (size_t)blockIdx.x * 32 : nullptr;
   TTS_STAMP(stp, 0);
+#ifdef TTS_STAMPS
+  if (stp && threadIdx.x == 0) stp[25] = t_first;  // (beside stamp 0: what the argument fetch cost)
+#endif
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int kq = wave % KSW;  // k-part within the workgroup (split-K combine through LDS)
@@ -372,20 +393,24 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
   // layout unit u >> 1; its waves load only that half's 8 columns of every tile (the other
   // lanes re-read the same 128-B pieces, no extra HBM bytes), so a matrix of 128 units
   // streams on 256 workgroups
-  const int cs2 = a.csplit == 2 ? 1 : 0;
-  const int bunits = (a.N >> 4) / NG;  // layout units
-  const int units = bunits << cs2;     // work units
+  const int cs2 = a.csplit >> 1;  // (csplit is 1 or 2)
+  const int units = a.units;          // work units
+  const int bunits = units >> cs2;    // layout units
   // K layout (StreamPlan::kc chunks, chunk-major): a wave's K part is kt_pc k-tiles of every
   // chunk; its stage st covers k-tiles kt(st) .. +KU-1 of chunk st / Sc.  K-sliced launches
   // (a.sliced) run chunk blockIdx.y only: a.K = one chunk, A = that chunk's columns.
-  const int kc = a.kc;
-  const int KT = a.sliced ? (a.K >> 5) * kc : (a.K >> 5) * SL;  // k-tiles of the whole matrix
-  const int KTc = KT / kc;
-  const int kt_pc = KTc / KSPLIT;
-  const int Sc = kt_pc / KU;
-  const int st_off = a.sliced ? blockIdx.y * Sc : 0;        // first (layout) stage of this launch
-  const int kt_base = a.sliced ? blockIdx.y * KTc : (SL > 1 ? (int)blockIdx.y * (a.K >> 5) : 0);  // first k-tile in A
-  const bf16_t* xg = a.x ? a.x + ((a.sliced || SL > 1) ? (size_t)blockIdx.y * a.K : 0) : nullptr;
+  // (the quotients are the host's, wgemm_derive: KT = kc * KTc, KTc = KSPLIT * kt_pc, kt_pc = KU * Sc)
+  const int KT = a.KT;  // k-tiles of the whole matrix
+  const int Sc = a.Sc;
+  const int kt_pc = Sc * KU;
+  const int KTc = kt_pc * KSPLIT;
+  // blockIdx.y: the K chunk of a sliced launch, the K slice of an SL > 1 one, else 0 (grid.y is 1):
+  // no test of a.sliced, nor of a.x (a launch always has its A) — each was a branch that split
+  // the argument fetch in two
+  const int by = (int)blockIdx.y;
+  const int st_off = SL > 1 ? 0 : by * Sc;  // first (layout) stage of this launch
+  const int kt_base = by * (a.K >> 5);      // first k-tile in A (sliced: KTc = a.K / 32)
+  const bf16_t* xg = a.x + (uint32_t)(by * a.K);
   const int ldxs = a.K + 8;  // +16 B per row: the 16 A rows land on distinct LDS bank slots
   const int ustride = nproj * UPW;  // (the fused launch's attention / o_proj workgroups excluded)
 
@@ -397,11 +422,11 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
   const int ur = a.ur;
   auto stile = [&](int uu, int st) -> long long {
     uu = min(uu, units - 1) >> cs2;
-    const int r = uu / ur, ui = uu - r * ur;
+    const int r = (int)fastdiv((uint32_t)uu, a.ur_div), ui = uu - r * ur;
     const int nr = min(ur, bunits - r * ur);
     return (long long)r * ur * KT * NG + (((long long)(st + st_off) * nr + ui) * KSPLIT + kpart) * NG * KU;
   };
-  const int S = a.sliced ? Sc : kc * Sc;  // stages per item in this launch
+  const int S = a.S;  // stages per item in this launch
 
   // ---- operands of the prologue and epilogue are loaded FIRST, the weight stream after:
   // vmcnt retires in issue order, so anything issued behind the stream could not be used
@@ -429,7 +454,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
 #pragma unroll
       for (int j = 0; j < EA; ++j) {  // all EA issued (clamped): a fixed load count keeps the
         const int c = min(tid + j * NT, achunks - 1);  // vmcnt waits below exact
-        const int m = c / kch, k = (c - m * kch) * 8;
+        const int m = (int)fastdiv_gt1((uint32_t)c, a.kch_div), k = (c - m * kch) * 8;
         xe[j] = *(const u32x4_t*)(xg + (size_t)m * a.ldx + k);
         if constexpr (NORM) ne[j] = *(const u32x4_t*)(a.normw + k);
       }
@@ -450,7 +475,8 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
       const int ppr = a.K >> 9;
       const int pieces = M * ppr;
       for (int p = wave; p < pieces; p += WAVES) {
-        const int m = p / ppr, kp = p - m * ppr;
+        // (p / ppr = 64 p / kch: K is a multiple of 512 here, so kch = 64 ppr)
+        const int m = (int)fastdiv_gt1((uint32_t)p << 6, a.kch_div), kp = p - m * ppr;
         __builtin_amdgcn_global_load_lds((gptr_t)(xg + (size_t)m * a.ldx + kp * 512 + lane * 8),
                                          (lptr_t)(xs + (size_t)m * ldxs + kp * 512), 16, 0, 0);
       }
@@ -481,6 +507,9 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
       }
     }
 
+  // (the position is a vector load behind a test: it stays here, ahead of the weight ring with
+  // the other operands — issued behind the primed stages the fused launch was 0.4 us slower,
+  // DESIGN section 7)
   uint32_t ftag = 0;  // fused attention: this launch's granule tag (row 0)
   if constexpr (FATT && EARLY) {
     if (a.fattn_wgs) ftag = ((uint32_t)a.fa.row_pos[0] << 6) | (uint32_t)a.fattn_layer;
@@ -526,7 +555,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
       for (int g = 0; g < NG; ++g)  // (aux 2: the non-temporal policy: streamed once per step)
         dst[kk][g] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (int)(q + (uint32_t)((g * KU + kk) * 1024)), 0, 2);
     if constexpr (AGR) {
-      const int sg = ps + st_off, ch = kc == 1 ? 0 : sg / Sc;
+      const int sg = ps + st_off, ch = a.kc == 1 ? 0 : (int)fastdiv((uint32_t)sg, a.sc_div);
       const int kt = ch * KTc + kpart * kt_pc + (sg - ch * Sc) * KU - kt_base;
 #pragma unroll
       for (int kk = 0; kk < KU; ++kk)
@@ -548,6 +577,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
 #pragma unroll
   for (int j = 0; j < R; ++j) issue(wr[j], ar[j]);
   __builtin_amdgcn_sched_barrier(0);
+  TTS_STAMP(stp, 26);  // (the primed stages issued)
 
   // ---- prologue: A rows in LDS (plain, RMSNorm'ed, or combined from attention chunks)
   if (a.diag & kWgemmDiagMask & 1) {
@@ -571,7 +601,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
       if (j < a_nj) {
         const int c = tid + j * NT;
         if (c < achunks) {
-          const int m = c / kch, k = (c - m * kch) * 8;
+          const int m = (int)fastdiv_gt1((uint32_t)c, a.kch_div), k = (c - m * kch) * 8;
           u32x4_t v = xe[j];
           if constexpr (NORM) {
             const int seg0 = (m * kch) >> 6, nseg = kch >> 6;
@@ -726,7 +756,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
       for (int mt = 0; mt < MT_MAX; ++mt) acc[g][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     auto consume = [&](const u32x4_t (&src)[KU][NG], const u32x4_t (&asrc)[KU][AGR ? MT_MAX : 1], int stage) {
-      const int sg = stage + st_off, ch = kc == 1 ? 0 : sg / Sc;
+      const int sg = stage + st_off, ch = a.kc == 1 ? 0 : (int)fastdiv((uint32_t)sg, a.sc_div);
       const int kt = ch * KTc + kpart * kt_pc + (sg - ch * Sc) * KU - kt_base;  // A column tile
 #pragma unroll
       for (int kk = 0; kk < KU; ++kk) {
@@ -971,7 +1001,8 @@ inline std::string wgemm_inst_name(int waves, int ku, int mt, int ng, int ksplit
 }
 
 template <int WAVES, int KU, int NG, int KSPLIT, int ASRC, bool NORM, int EPI, int R, bool EARLY>
-static void launch_one_e(const WgemmArgs& a, int grid, hipStream_t s) {
+static void launch_one_e(const WgemmArgs& a_in, int grid, hipStream_t s) {
+  WgemmArgs a = a_in;
   const int mt = a.M <= 16 ? 1 : (a.M <= 32 ? 2 : 4);
   const bool frows = !EARLY && a.fattn_wgs && a.M > 1;  // (FROWS: 2..16 rows)
   if (dry_launches()) {  // (the branches below, without the launch)
@@ -980,6 +1011,7 @@ static void launch_one_e(const WgemmArgs& a, int grid, hipStream_t s) {
   }
   size_t lds = (ASRC != A_GLOBAL) ? (((size_t)a.M * (a.K + 8) * 2 + 15) & ~(size_t)15) : 0;
   lds += (size_t)wgemm_red_floats(WAVES, KSPLIT, NG, mt, a.M, a.K) * sizeof(float);
+  const int nproj = grid;
   if (a.fattn_wgs) {  // QKV + fused decode attention (1..16 rows, D 64 / 128, 16-wave workgroups)
     if (!(EPI == EPI_STORE && ASRC == A_LDS && a.M >= 1 && a.M <= 16 && a.fa.D == wgemm_fattn_d(KU) &&
           WAVES == DEC_NW && a.gran && a.fattn_err && !a.sliced && a.csplit == 1 && a.fattn_wgs == a.M * a.fa.KVH))
@@ -1008,7 +1040,12 @@ static void launch_one_e(const WgemmArgs& a, int grid, hipStream_t s) {
     throw std::runtime_error("wgemm: tiled weight matrix above the 32-bit buffer range");
   if (ASRC == A_LDS && !EARLY && a.K % 512 != 0)
     throw std::runtime_error("wgemm: the LDS-DMA prologue needs K a multiple of 512 (plan_wgemm: A_GLOBAL)");
+  wgemm_derive(a, KU, NG, KSPLIT, KSPLIT, nproj, ASRC != A_GLOBAL);
   const dim3 g(grid, a.sliced ? a.kc : 1);
+  // the kernel offsets A by blockIdx.y * K without a test of a.x or a.sliced: a launch has its A,
+  // and grid.y is 1 unless blockIdx.y is the K chunk of a sliced launch
+  if (!a.x) throw std::runtime_error("wgemm: launch without an A operand");
+  if (g.y != 1 && !a.sliced) throw std::runtime_error("wgemm: grid.y > 1 on an unsliced launch");
   if (frows) {
     if constexpr (EPI == EPI_STORE && ASRC == A_LDS && WAVES == DEC_NW)
       hipLaunchKernelGGL((wgemm_kernel<WAVES, KU, 1, NG, KSPLIT, ASRC, NORM, EPI, R, false, KSPLIT, true>), g,

@@ -16,6 +16,8 @@ void launch_wgemm_kslice(const WgemmArgs& a_in, int units, hipStream_t s) {
     throw std::runtime_error("wgemm kslice: 1..32 rows, K / 4 a multiple of 512, kc 1, partial workspace");
   a.sliced = 0;
   a.csplit = 1;
+  if (!a.x) throw std::runtime_error("wgemm kslice: launch without an A operand");
+  wgemm_derive(a, 2, 1, 16, 4, (units + 1) / 2, true);
   const size_t lds = (((size_t)a.M * (a.K + 8) * 2 + 15) & ~(size_t)15) +
                      (size_t)wgemm_red_floats(8, 4, 1, 2, a.M, a.K) * sizeof(float);
   hipLaunchKernelGGL((wgemm_kernel<8, 2, 2, 1, 16, A_LDS, false, EPI_STORE, 2, false, 4>), dim3((units + 1) / 2, 4),

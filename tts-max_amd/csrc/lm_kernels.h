@@ -4,8 +4,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "fastdiv.h"
 
 namespace tts {
 
@@ -117,16 +120,44 @@ struct StepState {
 constexpr unsigned long long kWgemmMaxBytes = 0xFFFF0000ull;
 constexpr uint32_t kWgemmSentinel = 0xFFFFFFF0u;
 
-struct WgemmArgs {
+// Kernel-argument layout.  Everything a projection workgroup reads before its first weight load
+// sits in the first two 64-byte lines (the struct is 64-byte aligned, so is the kernel-argument
+// segment): the kernel fetches those two lines in one batch at its very top, ahead of the role
+// branch of the fused launch, and waits once.  Quotients of launch constants are computed by the
+// host (wgemm_derive below) and divisions by them in the kernel are multiply-high
+// pairs (fastdiv.h): the kernel holds no integer division.  Fields are ordered by when the
+// kernel needs them, NOT kept at stable offsets: a field added or moved here changes the
+// compiled code of every instantiation, deliberately (re-run tests/test_wgemm_prologue_isa.py).
+struct alignas(64) WgemmArgs {
+  // ---- line 0
   const bf16_t* x = nullptr;  // A: [M][ldx] bf16 activations
-  int M = 0, K = 0, ldx = 0;
   const bf16_t* w = nullptr;  // B: tiled weights (see lm_gemm.hip)
-  int N = 0;
   const bf16_t* normw = nullptr;  // RMSNorm weight [K] (NORM prologue)
+  bf16_t* resid = nullptr;  // EPI_RESID: residual stream, updated in place (read ahead of the weight stream)
+  unsigned long long* stamps = nullptr;  // diagnostic build only (TTS_STAMPS): [block][32]
+  int M = 0, K = 0, ldx = 0;
+  int N = 0;
+  int ldo = 0;
+  int ur = 0;         // layout: units per round (StreamPlan::ur, filled in by launch_wgemm)
+  // ---- line 1
+  int fattn_wgs = 0;  // attention workgroups appended to the grid (0: not fused), see below
+  int fo_units = 0;   // o_proj workgroups appended behind them, see below
+  int csplit = 1;     // 2: each 16-column unit runs as two 8-column halves (twice the workgroups; filled in by launch_wgemm)
+  int sliced = 0;     // 1: grid.y = K chunk, K = one chunk, ldx = full K (filled in by launch_wgemm)
+  int diag = 0;       // timing diagnostics only (TTS_WGEMM_DIAG): 1 no prologue, 2 no epilogue, 8 barrier before the stream, 64 per-wave norm-end stamps
+  // derived by the host for the instantiation that runs (wgemm_derive; callers leave them):
+  int KT = 0;         // k-tiles of the whole matrix
+  int Sc = 0;         // stages of a wave's K part in one K chunk (its k-tiles there: Sc * KU)
+  int S = 0;          // stages per item in this launch
+  int units = 0;      // work units ((N / 16 / NG) << (csplit == 2))
+  int nproj = 0;      // projection workgroups (grid.x without the fused launch's attention / o_proj ones)
+  FastDiv ur_div;     // / ur, dividends < layout units
+  FastDiv kch_div;    // / (K / 8), dividends <= M * K / 8
+  FastDiv sc_div;     // / Sc, dividends < stages of the whole K
+  // ---- needed behind the primed weight stages only
   float eps = 0.f;
   bf16_t* out = nullptr;  // [M][ldo]
-  int ldo = 0;
-  bf16_t* resid = nullptr;  // EPI_RESID: residual stream, updated in place
+  int kc = 1;         // layout: K chunks (StreamPlan::kc, filled in by launch_wgemm)
   // EPI_LOGITS
   const uint32_t* seen = nullptr;  // [M][seen_stride] bitmap of ids present in the sequence
   int seen_stride = 0;
@@ -139,9 +170,7 @@ struct WgemmArgs {
   const uint16_t* counts = nullptr;  // EPI_LOGITS: new-token counts [M][seen_stride*32] (frequency penalty)
   float freq_penalty = 0.f;
   int ldl = 0;
-  int ur = 0;         // layout: units per round (StreamPlan::ur, filled in by launch_wgemm)
-  int kc = 1;         // layout: K chunks (StreamPlan::kc, filled in by launch_wgemm)
-  int sliced = 0;     // 1: grid.y = K chunk, K = one chunk, ldx = full K (filled in by launch_wgemm)
+  const RowParams* row_par = nullptr;  // EPI_LOGITS_ROWS: [M] penalty / freq_penalty of each row (counts always set)
   float* part_out = nullptr;  // K-sliced launches: fp32 partials [kc][M][ldo] (caller's workspace)
   const bf16_t* next_norm = nullptr;  // K-sliced residual launches: RMSNorm the updated rows
   bf16_t* norm_out = nullptr;         //   with next_norm (eps) into norm_out [M][ldo]
@@ -153,7 +182,7 @@ struct WgemmArgs {
   // two consecutive launches, so a granule left by the previous launch never matches.
   uint64_t* gran = nullptr;   // [M][N / 2] q|k|v granules, then (fo_units) [M][H*D / 2] attention rows
   AttnArgs fa;                // the attention of this layer (its output row: fa.out)
-  int fattn_wgs = 0;          // attention workgroups appended to the grid (0: not fused)
+  FastDiv kvh_div;            // / fa.KVH, dividends < fattn_wgs (wgemm_derive)
   int fattn_layer = 0;
   // grid order: the projection workgroups, then the attention workgroups, then (fo_units > 0)
   // one o_proj workgroup per o_proj unit: every workgroup waits only on blocks of lower index,
@@ -169,14 +198,51 @@ struct WgemmArgs {
   // (2..16 rows: the attention rows' granules at gran + M*N/2, row m's H*D/2 at m*H*D/2;
   // o_proj's layout K chunks fo_kc; fo_resid holds the M hidden rows)
   const bf16_t* fo_w = nullptr;
-  int fo_units = 0, fo_ur = 0, fo_kc = 1;
+  int fo_ur = 0, fo_kc = 1;
+  int fo_Sc = 0;              // (2..16 rows) stages of an o_proj wave's K part in one chunk (wgemm_derive)
+  FastDiv fo_sc_div;          // / fo_Sc, dividends < the o_proj item's stages
   bf16_t* fo_resid = nullptr;
-  unsigned long long* stamps = nullptr;  // diagnostic build only (TTS_STAMPS): [block][8]
-  int csplit = 1;     // 2: each 16-column unit runs as two 8-column halves (twice the workgroups; filled in by launch_wgemm)
-  int diag = 0;       // timing diagnostics only (TTS_WGEMM_DIAG): 1 no prologue, 2 no epilogue, 8 barrier before the stream, 64 per-wave norm-end stamps
-  // (last: the fields above keep their kernel-argument offsets, so every other instantiation compiles as before)
-  const RowParams* row_par = nullptr;  // EPI_LOGITS_ROWS: [M] penalty / freq_penalty of each row (counts always set)
 };
+static_assert(offsetof(WgemmArgs, eps) == 128, "WgemmArgs: the prologue's fields fill the first two 64-byte lines");
+static_assert(offsetof(WgemmArgs, x) == 0 && offsetof(WgemmArgs, w) == 8, "WgemmArgs: x, w lead (tests/test_wgemm_prologue_isa.py)");
+static_assert(offsetof(WgemmArgs, fattn_wgs) == 64, "WgemmArgs: line 1 starts at the role split");
+
+// The launch constants the kernel would otherwise divide for (WgemmArgs: "derived by the
+// host"), for the instantiation (KU, NG, KSPLIT, KSW) that runs on `nproj` projection
+// workgroups: the quotients themselves, and the multiply-high pairs of the divisions whose
+// dividend is per workgroup, thread or stage, each made for the largest dividend the kernel
+// forms and refused (an error, never a wrong quotient) when no exact pair exists.
+// a_lds: the A rows are staged in LDS (only those prologues divide by K / 8).
+inline void wgemm_derive(WgemmArgs& a, int ku, int ng, int ksplit, int ksw, int nproj, bool a_lds) {
+  const int sl = ksplit / ksw;  // K slices over workgroups of the kc = 1 layouts
+  const int kc = a.kc;
+  a.KT = a.sliced ? (a.K >> 5) * kc : (a.K >> 5) * sl;
+  const int KTc = a.KT / kc, kt_pc = KTc / ksplit;
+  a.Sc = kt_pc / ku;
+  if (a.ur < 1 || a.Sc < 1 || a.Sc * ku * ksplit * kc != a.KT)
+    throw std::runtime_error("wgemm: K does not divide into the plan's stages");
+  if (a.csplit != 1 && a.csplit != 2) throw std::runtime_error("wgemm: csplit is 1 or 2");
+  a.S = a.sliced ? a.Sc : kc * a.Sc;
+  const int bunits = (a.N >> 4) / ng;
+  a.units = bunits << (a.csplit == 2 ? 1 : 0);
+  a.nproj = nproj;
+  const uint32_t kch = (uint32_t)a.K >> 3;
+  bool ok = fastdiv_make((uint32_t)a.ur, (uint32_t)bunits, &a.ur_div);  // uu >> cs2 < bunits
+  a.kch_div = FastDiv{};
+  if (a_lds)  // chunk c < M * kch; piece p * 64 < M * kch (fastdiv_gt1: kch > 1)
+    ok = kch > 1 && fastdiv_make(kch, (uint32_t)a.M * kch, &a.kch_div) && ok;
+  ok = fastdiv_make((uint32_t)a.Sc, (uint32_t)(kc * a.Sc), &a.sc_div) && ok;  // stage sg < kc * Sc
+  if (a.fattn_wgs) {
+    ok = a.fa.KVH > 0 && fastdiv_make((uint32_t)a.fa.KVH, (uint32_t)a.fattn_wgs, &a.kvh_div) && ok;
+    if (a.fo_units && a.M > 1) {  // the o_proj riding the 2..16-row launch (its shape: this launch's)
+      const int HD = a.fa.H * a.fa.D;
+      a.fo_Sc = ((HD >> 5) / a.fo_kc) / ksplit / ku;
+      const int fo_S = (HD >> 5) / (ksplit * ku);
+      ok = a.fo_Sc > 0 && fastdiv_make((uint32_t)a.fo_Sc, (uint32_t)fo_S, &a.fo_sc_div) && ok;
+    }
+  }
+  if (!ok) throw std::runtime_error("wgemm: no exact multiply-high pair for a launch divisor");
+}
 
 struct WgemmPlan {
   StreamPlan sp;  // the matrix's layout + launch shape (waves, stage depth, split-K)

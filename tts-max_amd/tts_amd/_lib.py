@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "tts_op_retile",
     "tts_op_wgemm",
     "tts_debug_step_plan",
+    "tts_debug_wgemm_plan",
     "tts_debug_step_plan_sampled",
     "tts_op_pgemm",
     "tts_op_sample",
@@ -208,6 +209,7 @@ def load_library() -> ctypes.CDLL:
         "tts_op_attn_prefill": (I32, [P, I32, pi32, pi32, pi32, I32, I32, P, P, I32, P, P, I32, I32, I32, F32, P, P, P]),
         "tts_op_attn_decode": (I32, [P, P, I32, I32, I32, P, P, I32, P, P, I32, P, P, I32, I32, I32, F32, P, P]),
         "tts_debug_step_plan": (I32, [ctypes.POINTER(LmConfig), I32, I32, ctypes.c_char_p, I32]),
+        "tts_debug_wgemm_plan": (I32, [I32, I32, I32, I32, I32, pi32]),
         "tts_debug_step_plan_sampled": (I32, [ctypes.POINTER(LmConfig), I32, I32, I32, ctypes.c_char_p, I32]),
         "tts_debug_step_plan_rows": (I32, [ctypes.POINTER(LmConfig), I32, I32, I32, ctypes.c_char_p, I32]),
     }
