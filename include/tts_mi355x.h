@@ -239,7 +239,8 @@ tts_status tts_lm_last_timing(tts_engine* e, float* prefill_ms, float* decode_ms
  * rows), 9 its int8 screen alone, 10 the sampled step's screened head (temperature 0.8, top_k
  * 50: the screen's top-k mode, its exact recompute and the list sampler; 1..16 rows, 1..8 at
  * hidden 4096), 11 the full sampling head (the lm_head with its logits store + the dense
- * sampler).  rows = batch rows, up to max_batch: above 64 rows every selector times what the
+ * sampler), 12 the fused launch's warm role as a launch of its own (TTS_WARM_STAGES = 0: none)
+ * followed by gate/up (scripts/warm_probe.py).  rows = batch rows, up to max_batch: above 64 rows every selector times what the
  * wide step runs at that row count (0..3 the tile GEMMs; 4 and 11 the tile lm_head, or with
  * TTS_WIDE_HEAD=0 the decode head in chunks; 5 the same row-generic attention).
  * Outputs: average ms per launch and the algorithmic HBM bytes one launch must move. */

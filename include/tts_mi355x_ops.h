@@ -113,6 +113,16 @@ tts_status tts_debug_step_plan(const tts_lm_config* cfg, int32_t rows, int32_t n
  * units, units per layout round (ur), launch grid, K chunks (kc), csplit, K-sliced, A rows in
  * LDS, launch shape index}: units > ur with units % ur != 0 is a partial last round. */
 tts_status tts_debug_wgemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t num_cu, int32_t* out);
+/* Diagnostics, no GPU needed: what the warm workgroups of the one-row fused QKV + attention +
+ * o_proj launch read of the tiled 2 FF x hidden gate/up matrix (N x K, the one-row SwiGLU plan
+ * on num_cu CUs): `stages` stages of every gate/up workgroup's stream, dealt over `wgs` warm
+ * workgroups (0, or at least 8), warm workgroup b taking the gate/up blocks g with g mod 8 ==
+ * (b + shift) mod 8.  info[8] = {stages after clamping, warm workgroups, gate/up workgroups,
+ * bytes of one workgroup's stage block, of the last workgroup's, bytes between stages, shift mod
+ * 8, stages per item}; out[cap][5] = {warm workgroup, byte offset, bytes, gate/up block, stage}
+ * per range, *n of them. */
+tts_status tts_debug_warm_plan(int32_t N, int32_t K, int32_t num_cu, int32_t stages, int32_t wgs, int32_t shift,
+                               int32_t* info, int64_t* out, int32_t cap, int32_t* n);
 /* ... of a sampled step (do_sample at temperature 0.8, top_p 1.0 and the given top_k in [1, 1024]):
  * the screened sampling head where it applies (head_screen_kernel<..., true> + sample_list_kernel),
  * else the full lm_head with its logits store (65..256 rows: the tile lm_head) + sample_kernel. */

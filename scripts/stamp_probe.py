@@ -70,6 +70,16 @@ for k in ("qkv", "o_proj", "gate_up", "down", "attention", "qkv_attn", "qkv_attn
         # (the o_proj workgroups come last in the grid; one row: "row 0 granules" = wave 0's
         # granules seen, "all rows" = its MFMAs done)
         no = arch.hidden_size // 16 if k == "qkv_attn_oproj" else 0
+        # (one row, o_proj riding: TTS_WARM_WGS warm workgroups behind the o_proj ones when
+        # TTS_WARM_STAGES > 0 — entry / loads issued / landed)
+        nw = 0
+        if no and rows == 1 and int(os.environ.get("TTS_WARM_STAGES", "0")) > 0:
+            nw = int(os.environ.get("TTS_WARM_WGS", "120"))
+            nw = nw if nw >= 8 else 0
+        if nw:
+            wm, us = us[len(us) - nw:], us[:len(us) - nw]
+            print(f"  warm        entry {q(wm[:, 0])}  issued {q(wm[:, 1])}  landed {q(wm[:, 3])}  "
+                  f"(first workgroup {wm[0, 0]:.2f} -> {wm[0, 3]:.2f}, last {wm[-1, 0]:.2f} -> {wm[-1, 3]:.2f})")
         nq = len(us) - na - no  # projection workgroups
         proj, cons = us[:nq], us[nq:nq + na]
         if no:

@@ -286,6 +286,27 @@ tts_status tts_debug_wgemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, in
   });
 }
 
+tts_status tts_debug_warm_plan(int32_t N, int32_t K, int32_t num_cu, int32_t stages, int32_t wgs, int32_t shift,
+                               int32_t* info, int64_t* out, int32_t cap, int32_t* n) {
+  return guarded([&] {
+    TTS_REQUIRE(info && out && n && num_cu > 0 && cap >= 0, "null argument");
+    TTS_REQUIRE(wgemm_supported(1, N, K, EPI_SWIGLU), "unsupported GEMM shape");
+    const WgemmPlan p = plan_wgemm(1, N, K, EPI_SWIGLU, num_cu);
+    const WarmArgs a = wgemm_warm_plan(p, nullptr, N, K, stages, wgs, shift);
+    const int32_t v[8] = {a.stages, a.wgs, a.nblk, (int32_t)a.blk_bytes, (int32_t)a.last_bytes, (int32_t)a.stage_bytes,
+                          a.shift, (K / 32) / (p.sp.ksplit * p.sp.ku)};
+    memcpy(info, v, sizeof v);
+    int rows = 0;
+    for (int b = 0; b < a.wgs; ++b)
+      warm_walk(a, b, [&](uint32_t off, uint32_t len, int g, int st) {
+        TTS_REQUIRE(rows < cap, "output buffer too small");
+        int64_t* r = out + (size_t)rows++ * 5;
+        r[0] = b; r[1] = off; r[2] = len; r[3] = g; r[4] = st;
+      });
+    *n = rows;
+  });
+}
+
 tts_status tts_debug_step_plan_sampled(const tts_lm_config* cfg, int32_t rows, int32_t num_cu, int32_t top_k,
                                        char* out, int32_t cap) {
   return guarded([&] {

@@ -31,7 +31,7 @@ void lm_bench_kernel(Engine* e, int which, int rows, int ctx, int iters, float* 
   TTS_REQUIRE(e->lm.loaded, "tts_lm_load has not been called");
   TTS_REQUIRE(rows >= 1 && rows <= e->w.cap_batch, "rows out of range");
   TTS_REQUIRE(ctx >= 1 && ctx <= e->lm.cfg.max_seq_len, "ctx out of range");
-  TTS_REQUIRE(which >= 0 && which <= 11 && iters >= 1, "bad kernel selector");
+  TTS_REQUIRE(which >= 0 && which <= 12 && iters >= 1, "bad kernel selector");
   hipStream_t s = e->stream;
   Ctx X(e, s);
   const tts_lm_config& c = X.c;
@@ -139,6 +139,11 @@ void lm_bench_kernel(Engine* e, int which, int rows, int ctx, int iters, float* 
         launch_bump_epoch(st.epoch, s);
         break;
       }
+      case 12:  // the warm role as a launch of its own (TTS_WARM_STAGES = 0: none), then gate/up
+        launch_warm_probe(X.warm_args(ly.wgu, 0), s);
+        X.gate_up(rows, ly);
+        b = 2.0 * 2 * FF * HID + act_rw * (HID + FF) + 2.0 * HID;
+        break;
     }
   };
   launch();

@@ -239,6 +239,7 @@ void launch_wgemm(const WgemmArgs& a_in, const WgemmPlan& p_in, int epi, bool no
   a.kc = p.sp.kc;
   a.sliced = p.sliced ? 1 : 0;
   a.csplit = p.csplit;
+  a.ring = p.ring;
   if (a.csplit == 2 && epi != EPI_STORE && epi != EPI_RESID)
     throw std::runtime_error("wgemm: column split only for plain store / residual launches");
   static const int diag = env_int("TTS_WGEMM_DIAG", 0);

@@ -304,6 +304,47 @@ TTS_DEV void fused_oproj_rows(const WgemmArgs& a, bf16_t* xs, float* red, int wa
   TTS_STAMP(stp, 3);
 }
 
+// ------------------------------------------- the warm role behind the o_proj workgroups -----
+// Warm workgroup b of the one-row fused launch (WarmArgs, lm_kernels.h): its waves share the
+// 1-KiB pieces of the blocks warm_walk deals it, each piece one LDS-DMA wave instruction (16 B a
+// lane, default cache policy: the lines stay in this XCD's L2) into one scratch KiB of the
+// workgroup's LDS — no registers held, nothing the compiler can delete, nothing read back.
+// Through a buffer resource over the matrix, as the weight stream: an offset past its end
+// returns zeros without touching memory.  No store, no poll, no other workgroup involved.
+TTS_DEV void warm_role(const WgemmArgs& a, char* smem, int b) {
+  unsigned long long* stp = a.stamps ? a.stamps + (size_t)blockIdx.x * 32 : nullptr;
+  TTS_STAMP(stp, 0);
+  const WarmArgs& wm = a.warm;
+  const uint32_t lane16 = (threadIdx.x & 63) * 16u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t nwav = blockDim.x >> 6;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)wm.w, (short)0, (int)wm.bytes, 0x00020000);
+  warm_walk(wm, b, [&](uint32_t off, uint32_t len, int, int) {
+    for (uint32_t q = wave * 1024u; q < len; q += nwav * 1024u)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)smem, 16, (int)lane16, (int)(off + q), 0, 0);
+  });
+  TTS_STAMP(stp, 1);  // (issued)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  TTS_STAMP(stp, 3);  // (landed)
+}
+
+#ifdef TTS_STAMPS
+// (diagnostic build) where the dispatcher put the workgroups: a histogram [kind][block][XCC id]
+// behind the stamps (kind 0: the one-row fused launch, 1: the one-row gate/up launch), summed over
+// every launch since the buffer was last read, and the distance (mod 8) between the XCC ids of
+// block 0 of a gate/up launch and of the fused launch before it (scripts/warm_xcd_probe.py)
+constexpr int kXccHist = 49152, kXccBlocks = 512, kXccLast = kXccHist - 1, kXccDist = kXccHist + 2 * kXccBlocks * 8;
+TTS_DEV void xcc_record(unsigned long long* stamps, int kind) {
+  if (!stamps || threadIdx.x != 0 || blockIdx.x >= kXccBlocks || blockIdx.y != 0) return;
+  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;  // HW_REG_XCC_ID
+  atomicAdd(stamps + kXccHist + ((size_t)kind * kXccBlocks + blockIdx.x) * 8 + xcc, 1ull);
+  if (blockIdx.x == 0) {
+    if (kind == 0) stamps[kXccLast] = xcc + 1;
+    else if (stamps[kXccLast]) atomicAdd(stamps + kXccDist + ((xcc + 8 - (unsigned)(stamps[kXccLast] - 1)) & 7u), 1ull);
+  }
+}
+#endif
+
 // ---------------------------------------------------------------- the GEMM kernel -----
 // One workgroup = WAVES waves; KSPLIT consecutive waves split the K range of one unit
 // (a unit = NG n-tiles of 16 output columns), WAVES/KSPLIT units run side by side, and
@@ -333,6 +374,11 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
                         ((EARLY && !FROWS && wgemm_fattn_d(KU) == 64) || (!EARLY && FROWS));
 #ifdef TTS_STAMPS
   const unsigned long long t_first = __builtin_amdgcn_s_memrealtime();  // (the kernel's first instruction)
+  if constexpr (FATT && EARLY && !FROWS) {
+    if (a.fattn_wgs) xcc_record(a.stamps, 0);
+  } else if constexpr (EPI == EPI_SWIGLU && MT_MAX == 1) {
+    if (a.M == 1) xcc_record(a.stamps, 1);
+  }
 #endif
   // The two argument lines of the prologue (WgemmArgs) are fetched here, in one batch ahead of
   // the role branch: the empty asm needs every field in a scalar register at this point, so
@@ -359,6 +405,12 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
       if (cb >= 0 && cb < a.fattn_wgs) {
         fattn_consumer<NT, wgemm_fattn_d(KU)>(a, smem, cb);
         return;
+      }
+      if constexpr (!FROWS) {  // (one row) the warm workgroups, behind the o_proj ones
+        if (cb >= a.fattn_wgs + a.fo_units) {
+          warm_role(a, smem, cb - a.fattn_wgs - a.fo_units);
+          return;
+        }
       }
       if (cb >= a.fattn_wgs) {  // o_proj unit cb - fattn_wgs
         const int lane = threadIdx.x & 63;
@@ -424,7 +476,7 @@ __global__ __launch_bounds__(WAVES * 64) void wgemm_kernel(WgemmArgs a) {
     uu = min(uu, units - 1) >> cs2;
     const int r = (int)fastdiv((uint32_t)uu, a.ur_div), ui = uu - r * ur;
     const int nr = min(ur, bunits - r * ur);
-    return (long long)r * ur * KT * NG + (((long long)(st + st_off) * nr + ui) * KSPLIT + kpart) * NG * KU;
+    return wgemm_stage_tile(r, ui, nr, st + st_off, kpart, ur, KT, NG, KSPLIT, KU);
   };
   const int S = a.S;  // stages per item in this launch
 
@@ -1034,6 +1086,12 @@ static void launch_one_e(const WgemmArgs& a_in, int grid, hipStream_t s) {
     }
     lds = std::max(lds, a.fa.D == 64 ? fattn_lds_bytes<64>() : fattn_lds_bytes<128>());
     grid += a.fattn_wgs + a.fo_units;
+    // the warm role: the one-row launch with o_proj riding only (wgemm_kernel's role dispatch)
+    if (a.warm.wgs && !(EARLY && a.M == 1 && a.fo_units && a.warm.w && a.warm.stages > 0 && a.warm.nblk > 0))
+      throw std::runtime_error("wgemm: warm workgroups ride the one-row launch that carries o_proj");
+    grid += a.warm.wgs;
+  } else if (a.warm.wgs) {
+    throw std::runtime_error("wgemm: warm workgroups without the fused launch");
   }
   if (lds > 160 * 1024) throw std::runtime_error("wgemm: LDS request above 160 KiB");
   if ((unsigned long long)a.N * (unsigned long long)(a.sliced ? (size_t)a.K * a.kc : (size_t)a.K) * 2ull > kWgemmMaxBytes)
@@ -1089,7 +1147,9 @@ static void launch_shape(const WgemmArgs& a, int grid, hipStream_t s) {
     // TTS-1 8 rows 808 -> 806 us, same ids (profiles/r4r_ab_ring4_*).
     // 17..32 rows too (two m-tiles, 164 registers, no spill): gate/up 17.42 -> 17.14 us, step
     // 993.4 -> 989.5 us at 32 rows, same ids (profiles/r5ring32_*)
-    if (a.M >= 4 && a.M <= 32 && S % 4 == 0) {
+    // one row (a.ring 4, Ctx::gate_up_ring4): the two stages behind the ones the fused launch's warm role
+    // left in L2 stream from HBM while the A row lands (same arithmetic order: same bits)
+    if (((a.M >= 4 && a.M <= 32) || (a.M == 1 && a.ring == 4)) && S % 4 == 0) {
       launch_one<h.waves, h.ku, NG, h.ksplit, ASRC, NORM, EPI, 4>(a, grid, s);
       return;
     }

@@ -66,6 +66,13 @@ __host__ __device__ inline long long plan_tile(int ng, int ksplit, int ku, int u
   return (long long)r * ur * KT * ng +
          (((long long)st * nr * ksplit + (long long)ui * ksplit + kp) * ng + g) * ku + kk;
 }
+// First tile of stage st of k-part kpart of the unit at place ui of layout round r (nr units in
+// that round): the one formula of the stage-major order, read by the decode kernel's weight
+// stream (wgemm_kernel: stile / soff) and by the host's warm plan (wgemm_warm_plan)
+__host__ __device__ inline long long wgemm_stage_tile(int r, int ui, int nr, int st, int kpart, int ur, int KT,
+                                                      int ng, int ksplit, int ku) {
+  return (long long)r * ur * KT * ng + (((long long)st * nr + ui) * ksplit + kpart) * ng * ku;
+}
 StreamPlan stream_plan(int N, int K, int ng, int num_cu);
 constexpr int LOGITS_MAX_PARTS = 1024;  // lm_head workgroups = argmax partials per row
 
@@ -119,6 +126,46 @@ struct StepState {
 // stage's tile offsets, at most 15 KiB below it) must stay beyond the matrix
 constexpr unsigned long long kWgemmMaxBytes = 0xFFFF0000ull;
 constexpr uint32_t kWgemmSentinel = 0xFFFFFFF0u;
+
+// ---- the warm role of the one-row fused QKV + attention + o_proj launch
+// Workgroups appended behind the o_proj ones start when the projection workgroups retire, i.e.
+// in the window in which only the attention chain runs and HBM idles.  They read the first
+// stages of this layer's gate/up stream with the default cache policy and exit: the lines stay
+// in the L2 of their XCD, where the gate/up workgroups of the next launch that land on the same
+// XCD find them.  They write nothing and wait on nothing; a wrong placement guess costs speed only.
+//
+// One gate/up workgroup's stage is one contiguous block of the stage-major layout (blk_bytes;
+// the last workgroup's may be shorter), a stage stage_bytes after the one before.  Blocks are
+// dealt round-robin over the 8 XCDs, so warm workgroup b takes the class c = (b + shift) mod 8
+// of gate/up blocks (g mod 8 == c), shares it with the other warm workgroups of the class, and
+// they deal its (stage, block) pairs among themselves, stage 0 first.
+struct WarmArgs {
+  const bf16_t* w = nullptr;  // the layer's tiled gate/up matrix
+  uint32_t bytes = 0;         // its size: the range of the buffer resource the reads go through
+  int wgs = 0;                // warm workgroups (0: no warm role)
+  int stages = 0;             // stages 0 .. stages-1 of every gate/up workgroup
+  int nblk = 0;               // gate/up workgroups (those with a unit)
+  uint32_t blk_bytes = 0, last_bytes = 0, stage_bytes = 0;
+  int shift = 0;
+};
+constexpr int kWarmXcds = 8;
+constexpr uint32_t kWarmMaxBytesPerXcd = 3u << 20;  // of an XCD's 4 MiB of L2
+// f(byte offset, bytes, gate/up block, stage) for every block warm workgroup b reads
+template <typename F>
+__host__ __device__ inline void warm_walk(const WarmArgs& a, int b, F f) {
+  const int c = (b + a.shift) & (kWarmXcds - 1);
+  const int nw = (a.wgs - (b & (kWarmXcds - 1)) + kWarmXcds - 1) / kWarmXcds;  // warm workgroups of the class
+  const int nb = c < a.nblk ? (a.nblk - c + kWarmXcds - 1) / kWarmXcds : 0;    // gate/up blocks of the class
+  if (nb == 0 || nw <= 0) return;
+  int st = 0, i = b / kWarmXcds;
+  for (;;) {
+    while (i >= nb && st < a.stages) { i -= nb; ++st; }
+    if (st >= a.stages) return;
+    const int g = c + kWarmXcds * i;
+    f((uint32_t)st * a.stage_bytes + (uint32_t)g * a.blk_bytes, g == a.nblk - 1 ? a.last_bytes : a.blk_bytes, g, st);
+    i += nw;
+  }
+}
 
 // Kernel-argument layout.  Everything a projection workgroup reads before its first weight load
 // sits in the first two 64-byte lines (the struct is 64-byte aligned, so is the kernel-argument
@@ -187,7 +234,7 @@ struct alignas(64) WgemmArgs {
   // grid order: the projection workgroups, then the attention workgroups, then (fo_units > 0)
   // one o_proj workgroup per o_proj unit: every workgroup waits only on blocks of lower index,
   // and blocks are dispatched in index order, so the launch completes whatever else occupies
-  // the GPU (no co-residency needed)
+  // the GPU (no co-residency needed); the warm workgroups (warm, below) come last and wait on nothing
   int* fattn_err = nullptr;   // set to 1 if a granule wait timed out; later waits then give up at once
   int fattn_spins = 1 << 16;  // polls (s_sleep 1 each, ~0.1 s in all) before a wait gives up
   // o_proj fused behind the attention (fo_units > 0): the attention workgroups also publish
@@ -202,6 +249,11 @@ struct alignas(64) WgemmArgs {
   int fo_Sc = 0;              // (2..16 rows) stages of an o_proj wave's K part in one chunk (wgemm_derive)
   FastDiv fo_sc_div;          // / fo_Sc, dividends < the o_proj item's stages
   bf16_t* fo_resid = nullptr;
+  int ring = 0;  // (host only) 4: the four-stage ring for the one-row gate/up launch (launch_shape; WgemmPlan::ring)
+  // the warm role (one row, o_proj riding): warm.wgs workgroups behind the o_proj ones read the first
+  // stages of the layer's gate/up stream into their XCD's L2 (WarmArgs).  Last in the struct: no
+  // other role's fetch touches these lines
+  WarmArgs warm;
 };
 static_assert(offsetof(WgemmArgs, eps) == 128, "WgemmArgs: the prologue's fields fill the first two 64-byte lines");
 static_assert(offsetof(WgemmArgs, x) == 0 && offsetof(WgemmArgs, w) == 8, "WgemmArgs: x, w lead (tests/test_wgemm_prologue_isa.py)");
@@ -251,7 +303,44 @@ struct WgemmPlan {
   bool a_lds = true;
   bool sliced = false;  // one K chunk per workgroup (grid.y = sp.kc) + combine kernel
   int csplit = 1;       // 2: units split into 8-column halves over twice the workgroups
+  int ring = 0;         // 4: the one-row gate/up launch on the four-stage ring (TTS_GU_RING); 0: the shape's
 };
+
+// The warm role's arguments (WarmArgs, above) for the one-row gate/up launch of plan p over the
+// tiled N x K matrix w: stages 0 .. W-1 of every gate/up workgroup's stream (its first units),
+// read by wgs warm workgroups under the placement rule `shift`.  W is clamped to the item's stage
+// count and to what kWarmMaxBytesPerXcd holds of one XCD's blocks; wgs is 0 (no warm role) or at
+// least 8 (every class of blocks needs a warm workgroup).  The offsets are wgemm_stage_tile's.
+inline WarmArgs wgemm_warm_plan(const WgemmPlan& p, const bf16_t* w, int N, int K, int W, int wgs, int shift) {
+  const StreamPlan& s = p.sp;
+  if (wgs < 0 || (wgs > 0 && wgs < kWarmXcds)) throw std::runtime_error("warm plan: 0 or at least 8 warm workgroups");
+  if (p.sliced || p.csplit != 1 || p.grid != s.grid || N <= 0 || K <= 0 || N % (16 * s.ng) || K % (32 * s.ksplit * s.ku) ||
+      (unsigned long long)N * (unsigned long long)K * 2ull > kWgemmMaxBytes)
+    throw std::runtime_error("warm plan: not a plain one-round-order launch of a tiled matrix");
+  const int upw = s.waves / s.ksplit, units = (N / 16) / s.ng, KT = K / 32, ur = s.ur();
+  const int S = KT / (s.ksplit * s.ku);
+  const int nr = ur < units ? ur : units;  // the first round's units: where every workgroup's stream starts
+  auto at = [&](int ui, int st) {
+    return (uint32_t)((unsigned long long)wgemm_stage_tile(0, ui, nr, st, 0, ur, KT, s.ng, s.ksplit, s.ku) * 1024ull);
+  };
+  WarmArgs a;
+  a.w = w;
+  a.bytes = (uint32_t)((unsigned long long)(N / 16) * KT * 1024ull);
+  a.nblk = (nr + upw - 1) / upw;
+  a.blk_bytes = at(upw, 0);
+  a.last_bytes = at(nr - (a.nblk - 1) * upw, 0);
+  a.stage_bytes = at(0, 1);
+  const uint32_t per_xcd = (uint32_t)((a.nblk + kWarmXcds - 1) / kWarmXcds) * a.blk_bytes;
+  const int fit = (int)(kWarmMaxBytesPerXcd / per_xcd);
+  W = W < S ? W : S;
+  W = W < fit ? W : fit;
+  a.stages = (wgs > 0 && W > 0) ? W : 0;
+  a.wgs = a.stages ? wgs : 0;
+  a.shift = ((shift % kWarmXcds) + kWarmXcds) % kWarmXcds;
+  return a;
+}
+
+void launch_warm_probe(const WarmArgs& warm, hipStream_t s);  // the warm role alone (lm_gemm_swiglu.hip)
 
 // Row-major W [N][K] -> tiles of the matrix's stream plan.  The destination matrix has
 // N_total rows; source n-tile nt lands at n-tile nt * nt_mult + nt_off (nt_mult = 2

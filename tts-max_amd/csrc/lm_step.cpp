@@ -113,6 +113,7 @@ bool Ctx::gemm(const Gemm& g) {
       p.sliced = false;  // wide outputs (teacher-forced scoring over the vocabulary):
       p.a_lds = false;   // A rows from global memory instead of fp32 chunk partials
     }
+    if (epi == EPI_SWIGLU && rows == 1 && gate_up_ring4()) p.ring = 4;
     const bf16_t* xin = x ? x + (size_t)r0 * K : nullptr;
     bool norm = normw != nullptr;
     // fused RMSNorm only where the rows sit in registers (<= 16 rows, the early prologue):
@@ -222,6 +223,28 @@ bool Ctx::fused_attn_ok(int rows, bool decode) const {
   static const int max_rows = env_int("TTS_FATTN_ROWS", 16);
   return rows <= std::min(16, max_rows) && wgemm_fattn_rows_ok(rows, QKV(), c.hidden_size, c.head_dim, e->num_cu);
 }
+// The warm role of the one-row fused launch (lm_kernels.h WarmArgs): TTS_WARM_STAGES=<W> stages of
+// the layer's gate/up stream (default 2 = 2 MiB per XCD; 0: no warm workgroups; 3 was slower
+// than none: the reads outlast the attention and delay o_proj's hand-off, profiles/warm_ab.txt)
+// read by TTS_WARM_WGS workgroups behind the o_proj ones.  TTS_WARM_XCD_DIST: the XCDs between
+// block 0 of the fused launch and block 0 of the gate/up launch behind it as the dispatcher deals
+// them (0 in every launch measured, profiles/warm_xcd_placement.txt).
+// The one-row gate/up launch behind that fused launch runs on the four-stage ring its 4..32-row
+// form has (launch_shape), so the two stages behind the warm ones stream from HBM while the A row
+// lands; TTS_GU_RING=2 keeps the two-stage ring.  Same arithmetic order: same bits.
+bool Ctx::gate_up_ring4() const {
+  static const bool on = env_int("TTS_GU_RING", 4) != 2;
+  return on && fused_attn_ok(1, true) && fused_oproj_ok();
+}
+WarmArgs Ctx::warm_args(const bf16_t* wgu, int first_block) const {
+  static const int stages = env_int("TTS_WARM_STAGES", 2);
+  static const int wgs = env_int("TTS_WARM_WGS", 120);
+  static const int dist = env_int("TTS_WARM_XCD_DIST", 0);
+  if (stages <= 0 || wgs < kWarmXcds) return WarmArgs{};
+  const WgemmPlan pg = plan_wgemm(1, 2 * c.intermediate_size, c.hidden_size, EPI_SWIGLU, e->num_cu);
+  // warm workgroup b is block first_block + b of its grid, `dist` XCDs before the gate/up block of that index
+  return wgemm_warm_plan(pg, wgu, 2 * c.intermediate_size, c.hidden_size, stages, wgs, first_block - dist);
+}
 WgemmArgs Ctx::fused_attn_args(const AttnArgs& a, int layer, bool with_oproj) {
   WgemmArgs fx;
   fx.gran = w.gran.as<uint64_t>();
@@ -240,6 +263,8 @@ WgemmArgs Ctx::fused_attn_args(const AttnArgs& a, int layer, bool with_oproj) {
     fx.fo_ur = po.sp.ur();
     fx.fo_kc = po.sp.kc;
     fx.fo_resid = w.x.as<bf16_t>();
+    if (a.rows == 1)  // (the fused launch runs the QKV plan's whole-unit grid, launch_wgemm)
+      fx.warm = warm_args(ly.wgu, plan_wgemm(1, QKV(), c.hidden_size, EPI_STORE, e->num_cu).sp.grid + fx.fattn_wgs + fx.fo_units);
   }
   return fx;
 }

@@ -88,6 +88,10 @@ struct Ctx {
   AttnArgs attn_args(int layer, int rows, const int* slot, const int* pos, bool qkv_part = false);
   bool fused_attn_ok(int rows, bool decode) const;
   WgemmArgs fused_attn_args(const AttnArgs& a, int layer, bool with_oproj = false);
+  // the warm role riding that launch at one row: wgu = the layer's gate/up weights, first_block =
+  // the grid index of the first warm workgroup (all-zero: no warm role)
+  WarmArgs warm_args(const bf16_t* wgu, int first_block) const;
+  bool gate_up_ring4() const;  // the one-row gate/up launch behind it on the four-stage ring (TTS_GU_RING)
   bool fused_oproj_ok() const;
   bool fused_oproj_rows_ok(int rows) const;
   void layers(int rows, const int* slot, const int* pos, bool decode);  // one stack pass over w.x

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "tts_debug_step_plan",
     "tts_debug_wgemm_plan",
     "tts_debug_step_plan_sampled",
+    "tts_debug_warm_plan",
     "tts_op_pgemm",
     "tts_op_sample",
     "tts_op_sample_list",
@@ -212,6 +213,7 @@ def load_library() -> ctypes.CDLL:
         "tts_debug_wgemm_plan": (I32, [I32, I32, I32, I32, I32, pi32]),
         "tts_debug_step_plan_sampled": (I32, [ctypes.POINTER(LmConfig), I32, I32, I32, ctypes.c_char_p, I32]),
         "tts_debug_step_plan_rows": (I32, [ctypes.POINTER(LmConfig), I32, I32, I32, ctypes.c_char_p, I32]),
+        "tts_debug_warm_plan": (I32, [I32, I32, I32, I32, I32, I32, pi32, ctypes.POINTER(ctypes.c_int64), I32, pi32]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("TTS_LIB_PATH") and not hasattr(lib, name):

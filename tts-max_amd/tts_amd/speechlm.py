@@ -385,7 +385,7 @@ class MI355XSpeechLM:
         # sample_screened / sample_full: the sampled step's head (T 0.8, top_k 50) through the
         # int8 screen + list sampler / the full lm_head with its logits store + dense sampler
         sel = {"qkv_attn": 6, "qkv_attn_oproj": 7, "head_screened": 8, "head_screen": 9,
-               "sample_screened": 10, "sample_full": 11}.get(which)
+               "sample_screened": 10, "sample_full": 11, "warm_gate_up": 12}.get(which)
         sel = self.KERNELS.index(which) if sel is None else sel
         _lib.check(self._lib.tts_lm_bench_kernel(self._h, sel, rows, ctx, iters,
                                                  ctypes.byref(ms), ctypes.byref(b)))
