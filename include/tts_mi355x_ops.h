@@ -181,6 +181,38 @@ tts_status tts_op_gemm_f32(const float* A, int32_t M, int32_t K, int32_t lda, co
                            int32_t N, const float* bias, float* C, int32_t ldc,
                            const float* resid, int32_t act, void* stream);
 
+/* planes[0..3n) = the (h, m, l) bf16 split of x[0..n) the codec GEMMs apply to their operands
+ * (h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), round to nearest even; h + m + l == x):
+ * split_planes_kernel alone, as the engine runs it over the weights at load. */
+tts_status tts_op_split_planes(const float* x, uint16_t* planes, int64_t n, void* stream);
+
+/* One codec GEMM kernel form alone: C[M][ldc] = act(A . B^T + bias) (+ resid), every operand the
+ * engine's GemmF32Args carries.  A [M rows, lda apart][K] fp32 and / or Ap, its bf16 planes with
+ * A's addressing (element (m, k) of plane p at Ap + p * ap_plane + m * lda + k); B [N][K] fp32
+ * and / or Bp = planes [3][N][K] (tts_op_split_planes); bias [N], resid [M][ldc] optional; act 0
+ * none, 1 swish.  Output: C fp32 and / or Cp, the planes of the stored value (element (m, n) of
+ * plane p at Cp + p * cp_plane + m * ldc + n).  lda may be < K (the sliding-window conv operand).
+ *
+ * form -1: the engine's own choice, through its two wrappers: A NULL (Ap, Bp) -> launch_gemm_x3p
+ * (tile by size and TTS_CODEC_X3P_*), else (A, B, optional Bp / Ap) -> launch_gemm_f32.
+ * Any other value names one instantiation:
+ *   gemm_x3p_kernel (Ap and Bp): tile | schedule << 3 | 0x20 (PP) | 0x40 (four stages), tile 0..5 =
+ *     256x128, 128x128, 128x64, 64x64, 32x32, 128x128 on 8 waves with three stages; schedule 0 =
+ *     two-stage DMA (ILV off), 1 = one stage ahead between the MFMAs (ILV on), 2 = the tile's own.
+ *     PP exists on tile 0 with ILV, four stages on tile 4, three and four stages with ILV only.
+ *   gemm_bx3_kernel: 0x100 + i, i = 0 256x128 Ap Bp, 1 128x128 Ap Bp, 2 256x128 A Bp,
+ *     3 128x256 A Bp, 4 128x128 A Bp, 5 64x64 A Bp, 6 128x128 A B, 7 64x64 A B.
+ *   gemm_f32_kernel (fp32 MFMA; A, B): 0x200 + i, i = 0 64x64 K step 64, 1 64x64 K step 16,
+ *     2 128x128 K step 32, 3 128x128 K step 16.
+ * Rejected with an error and no launch: an operand the form reads missing, K % 32 != 0 for a
+ * bf16-split form (K no multiple of the K step for an fp32 form), PP / four stages / ILV off on a
+ * tile that has no such kernel, lda % 8 != 0 or a base or plane stride off 16 bytes for planes
+ * (lda % 4, 16 bytes for fp32 operands), an unknown form. */
+tts_status tts_op_gemm_planes(const float* A, const uint16_t* Ap, int64_t ap_plane, int32_t M, int32_t K, int32_t lda,
+                              const float* B, const uint16_t* Bp, int32_t N, const float* bias, float* C,
+                              uint16_t* Cp, int64_t cp_plane, int32_t ldc, const float* resid, int32_t act,
+                              int32_t form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

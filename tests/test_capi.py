@@ -67,6 +67,50 @@ def test_attention_ops_reject_unsupported_shapes_before_any_gpu_call():
     assert b"exactly one" in lib.tts_last_error()
 
 
+def test_codec_gemm_op_rejects_what_a_form_cannot_run_before_any_gpu_call():
+    """tts_op_gemm_planes names one kernel instantiation; a combination that instantiation cannot
+    run is an error on the host, with nothing launched (the pointers are never dereferenced)."""
+    from oracle import codec_gemm_oracle as go
+    from tts_amd import _lib
+
+    lib = _lib.load_library()
+    assert {"tts_op_split_planes", "tts_op_gemm_planes"} <= set(_lib.EXPORTED_SYMBOLS)
+    p = 0x1000
+
+    def gemm(form, A=p, Ap=p, B=p, Bp=p, M=70, N=68, K=64, lda=64, C=p, Cp=None, ap_plane=8192):
+        return lib.tts_op_gemm_planes(A, Ap, ap_plane, M, K, lda, B, Bp, N, None, C, Cp, 8192, N, None, 0, form, None)
+
+    x3p, bx3, f32 = go.FORMS["x3p_t1_ilv1"][0], go.FORMS["bx3_64x64"][0], go.FORMS["f32_64x64_k64"][0]
+    for kw, form, word in (
+            (dict(), go.x3p_form(1, 1, pp=True), b"PP needs the 8-wave"),       # PP off the 8-wave tile
+            (dict(), go.x3p_form(0, 0, pp=True), b"PP needs the 8-wave"),       # PP without ILV
+            (dict(), go.x3p_form(3, -1, four=True), b"four stages"),
+            (dict(), go.x3p_form(5, 0), b"one-stage-ahead schedule only"),
+            (dict(), 6, b"tile 0..5"),
+            (dict(Ap=None), x3p, b"planes missing"),
+            (dict(Bp=None), x3p, b"planes missing"),
+            (dict(K=48, lda=48), x3p, b"K % 32"),
+            (dict(lda=36), x3p, b"lda % 8"),
+            (dict(Ap=p + 2), x3p, b"unaligned"),
+            (dict(ap_plane=8196), x3p, b"ap_plane % 8"),
+            (dict(K=48, lda=48), bx3, b"32-element steps"),
+            (dict(B=None), bx3, b"fp32 B"),
+            (dict(A=None), go.FORMS["bx3_64x64_Bp"][0], b"fp32 A"),
+            (dict(Ap=None), go.FORMS["bx3_128x128_ApBp"][0], b"A's planes"),
+            (dict(Bp=None), go.FORMS["bx3_256x128_Bp"][0], b"B's planes"),
+            (dict(K=96, lda=96), f32, b"K step"),
+            (dict(K=40, lda=40), go.FORMS["f32_128x128_k16"][0], b"K step"),
+            (dict(A=None), f32, b"fp32 A and B"),
+            (dict(lda=62), bx3, b"lda % 4"),
+            (dict(C=None), bx3, b"no output"),
+            (dict(M=0), bx3, b"bad shape"),
+            (dict(), 0x300, b"unknown form"), (dict(), 0x108, b"unknown form"), (dict(), -2, b"unknown form"),
+            (dict(A=None, Bp=None), -1, b"planes missing")):
+        assert gemm(form, **kw) != 0, (kw, form)
+        assert word in lib.tts_last_error(), (kw, form, lib.tts_last_error())
+    assert lib.tts_op_split_planes(None, p, 8, None) != 0 and lib.tts_op_split_planes(p, p, 0, None) != 0
+
+
 def test_struct_layouts_match_header():
     from tts_amd import _lib
 

@@ -741,4 +741,59 @@ tts_status tts_op_gemm_f32(const float* A, int32_t M, int32_t K, int32_t lda, co
   });
 }
 
+tts_status tts_op_split_planes(const float* x, uint16_t* planes, int64_t n, void* stream) {
+  return guarded([&] {
+    TTS_REQUIRE(x && planes && n >= 1, "null argument");
+    launch_split_planes(x, planes, (long long)n, (hipStream_t)stream);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+tts_status tts_op_gemm_planes(const float* A, const uint16_t* Ap, int64_t ap_plane, int32_t M, int32_t K, int32_t lda,
+                              const float* B, const uint16_t* Bp, int32_t N, const float* bias, float* C,
+                              uint16_t* Cp, int64_t cp_plane, int32_t ldc, const float* resid, int32_t act,
+                              int32_t form, void* stream) {
+  return guarded([&] {
+    TTS_REQUIRE(M >= 1 && N >= 1 && K >= 1, "bad shape: M, N, K >= 1");
+    TTS_REQUIRE(A || Ap, "planes missing: neither A nor Ap");
+    TTS_REQUIRE(B || Bp, "planes missing: neither B nor Bp");
+    TTS_REQUIRE(C || Cp, "no output: neither C nor Cp");
+    TTS_REQUIRE(ldc >= N && lda >= 1, "ldc < N or lda < 1");
+    TTS_REQUIRE(act == 0 || act == 1, "act is 0 or 1");
+    // the kernels' 16-byte loads: fp32 rows in float4, plane rows in 8 bf16
+    TTS_REQUIRE(!A || (lda % 4 == 0 && ((size_t)A & 15) == 0), "A: lda % 4 != 0 or an unaligned base");
+    TTS_REQUIRE(!Ap || (lda % 8 == 0 && ap_plane % 8 == 0 && ((size_t)Ap & 15) == 0),
+                "Ap: lda % 8 != 0, ap_plane % 8 != 0 or an unaligned base");
+    TTS_REQUIRE(K % 4 == 0 && ((size_t)B & 15) == 0 && ((size_t)Bp & 15) == 0, "B / Bp: K % 4 != 0 or an unaligned base");
+    TTS_REQUIRE(!Bp || K % 8 == 0, "Bp: K % 8 != 0");
+    GemmF32Args g;
+    g.A = A; g.Ap = Ap; g.ap_plane = ap_plane; g.M = M; g.K = K; g.lda = lda;
+    g.B = B; g.Bp = Bp; g.N = N; g.bias = bias;
+    g.C = C; g.Cp = Cp; g.cp_plane = cp_plane; g.ldc = ldc; g.resid = resid; g.act = act;
+    hipStream_t s = (hipStream_t)stream;
+    if (form == -1) {  // the engine's wrappers: planes-only A is gemm_p's call, else gemm's
+      if (!A) {
+        TTS_REQUIRE(Bp, "planes missing: Ap without Bp");
+        launch_gemm_x3p(g, s);
+      } else {
+        TTS_REQUIRE(B, "fp32 A needs fp32 B (Bp beside it is optional)");
+        TTS_REQUIRE(K % 16 == 0, "K % 16 != 0");
+        launch_gemm_f32(g, s);
+      }
+    } else if (form >= 0 && form < 0x80) {
+      TTS_REQUIRE(Ap && Bp, "planes missing: the x3p forms read Ap and Bp");
+      const int sched = (form >> 3) & 3;
+      TTS_REQUIRE(sched != 3, "unknown form");
+      launch_gemm_x3p_form(g, form & 7, sched == 2 ? -1 : sched, (form & 0x20) != 0, (form & 0x40) != 0, s);
+    } else if (form >= 0x100 && form < 0x100 + kF32_64x64) {
+      launch_gemm_f32_form(g, form - 0x100, s);
+    } else if (form >= 0x200 && form < 0x200 + (kGemmForms - kF32_64x64)) {
+      launch_gemm_f32_form(g, kF32_64x64 + form - 0x200, s);
+    } else {
+      TTS_REQUIRE(false, "unknown form");
+    }
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
 }  // extern "C"

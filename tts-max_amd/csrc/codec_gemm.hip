@@ -379,28 +379,22 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_x3p_kernel(GemmF32Args g) {
 #endif
 }
 
+// ilv: the one-stage-ahead schedule with the DMA between the MFMAs; else the two-stage schedule
+// (NS == 2 only).  pp: the out-of-phase DMA split (PP, above): 8 waves, two stages, ilv
 template <int TM, int TN, int WM, int WN, int NS = 2>
-static void launch_x3p(const GemmF32Args& g, hipStream_t s) {
+static void launch_x3p(const GemmF32Args& g, bool ilv, bool pp, hipStream_t s) {
   constexpr size_t lds = NS * 3 * (size_t)(TM + TN) * 64;
   static_assert(lds <= 160 * 1024, "LDS");
   const int tiles = ((g.M + TM - 1) / TM) * ((g.N + TN - 1) / TN);
-  // the one-stage-ahead schedule with the DMA between the MFMAs on the 8- and 4-wave 64x64-per-
-  // wave tiles (a step is long enough to cover the DMA's latency); the two-stage schedule on
-  // the small tiles, whose steps are not (one 650-code utterance 4.8 -> 5.3 ms with the first,
-  // profiles/r5h_ab_codec_ilv.txt).  TTS_CODEC_X3P_ILV=0 / 1 forces one (A/B)
-  static const int ilv_env = env_int("TTS_CODEC_X3P_ILV", -1);
-  const bool ilv = NS >= 3 || (ilv_env >= 0 ? ilv_env != 0 : (TM / WM == 64 && TN / WN == 64));
-  // TTS_CODEC_X3P_PP=1: the out-of-phase DMA split (PP, above) on the 8-wave tile (experiment)
-  static const bool pp = env_set("TTS_CODEC_X3P_PP");
-  if (ilv && pp && NS == 2 && WM * WN == 8)
-    hipLaunchKernelGGL((gemm_x3p_kernel<TM, TN, WM, WN, true, NS, WM * WN == 8>), dim3(tiles), dim3(64 * WM * WN), lds, s, g);
-  else if (ilv) hipLaunchKernelGGL((gemm_x3p_kernel<TM, TN, WM, WN, true, NS>), dim3(tiles), dim3(64 * WM * WN), lds, s, g);
-  else hipLaunchKernelGGL((gemm_x3p_kernel<TM, TN, WM, WN, false>), dim3(tiles), dim3(64 * WM * WN), lds, s, g);
-}
-
-static bool small4() {
-  static const bool v = env_set("TTS_CODEC_X3P_SMALL4");
-  return v;
+  if constexpr (NS == 2 && WM * WN == 8) {
+    if (pp) {
+      hipLaunchKernelGGL((gemm_x3p_kernel<TM, TN, WM, WN, true, NS, true>), dim3(tiles), dim3(64 * WM * WN), lds, s, g);
+      return;
+    }
+  }
+  if (ilv) hipLaunchKernelGGL((gemm_x3p_kernel<TM, TN, WM, WN, true, NS>), dim3(tiles), dim3(64 * WM * WN), lds, s, g);
+  else if constexpr (NS == 2)
+    hipLaunchKernelGGL((gemm_x3p_kernel<TM, TN, WM, WN, false>), dim3(tiles), dim3(64 * WM * WN), lds, s, g);
 }
 
 bool gemm_x3p_supported(const GemmF32Args& g) {
@@ -408,31 +402,56 @@ bool gemm_x3p_supported(const GemmF32Args& g) {
   return g.Ap && g.Bp && g.K % 32 == 0 && g.lda % 8 == 0 && ((size_t)g.Ap & 15) == 0 && g.M >= 1 && g.N >= 1;
 }
 
-void launch_gemm_x3p(const GemmF32Args& g, hipStream_t s) {
+// One named instantiation.  tile 0..5: 256x128 (8 waves of 64x64), 128x128, 128x64, 64x64 (4
+// waves), 32x32 (one wave), 128x128 on 8 waves of 64x32 with three stages (experiment).  ilv: 0 the
+// two-stage schedule, 1 the one-stage-ahead schedule, -1 the tile's own: the one-stage-ahead
+// schedule on the 8- and 4-wave 64x64-per-wave tiles (a step is long enough to cover the DMA's
+// latency); the two-stage schedule on the small tiles, whose steps are not (one 650-code
+// utterance 4.8 -> 5.3 ms with the first, profiles/r5h_ab_codec_ilv.txt).  pp: the out-of-phase
+// DMA split (tile 0 with ilv only).  four: four stages, the DMA three steps ahead (tile 4 only).
+// The three- and four-stage forms exist with the one-stage-ahead schedule only.
+void launch_gemm_x3p_form(const GemmF32Args& g, int tile, int ilv, bool pp, bool four, hipStream_t s) {
   if (!gemm_x3p_supported(g)) throw std::runtime_error("gemm_x3p: A and B planes, K % 32 == 0, 16-B aligned rows");
+  if (tile < 0 || tile > 5) throw std::runtime_error("gemm_x3p: tile 0..5");
+  const bool own = tile == 0 || tile == 1 || tile == 3;  // 64x64 per wave
+  const bool on = tile == 5 || four || (ilv >= 0 ? ilv != 0 : own);
+  if ((tile == 5 || four) && ilv == 0) throw std::runtime_error("gemm_x3p: three and four stages run the one-stage-ahead schedule only");
+  if (pp && (tile != 0 || !on)) throw std::runtime_error("gemm_x3p: PP needs the 8-wave 256x128 tile and the one-stage-ahead schedule");
+  if (four && tile != 4) throw std::runtime_error("gemm_x3p: four stages exist for the one-wave tile only");
+  switch (tile) {
+    case 0: launch_x3p<256, 128, 4, 2>(g, on, pp, s); break;
+    case 1: launch_x3p<128, 128, 2, 2>(g, on, false, s); break;
+    case 2: launch_x3p<128, 64, 2, 2>(g, on, false, s); break;
+    case 3: launch_x3p<64, 64, 2, 2>(g, on, false, s); break;
+    case 5: launch_x3p<128, 128, 2, 4, 3>(g, true, false, s); break;
+    default:
+      if (four) launch_x3p<32, 32, 1, 1, 4>(g, true, false, s);
+      else launch_x3p<32, 32, 1, 1>(g, on, false, s);
+      break;
+  }
+}
+
+void launch_gemm_x3p(const GemmF32Args& g, hipStream_t s) {
   // tiles: 256x128 (8 waves of 64x64, one workgroup per CU) where that makes >= 2 rounds of
   // the CUs (the ragged batch's big GEMMs); else 128x128, 128x64, 64x64 (4 waves) or 32x32 (one
   // wave) down to what fills the chip (every tile sweeps an output's K in the same order: the
   // same bits; a lone utterance's tile choices swept in profiles/r5w_ab_codec1_tile.txt, and
   // 64x64 from half a round, r5z2_ab_codec1_heur.txt, measured the same).  TTS_CODEC_X3P_TILE
-  // forces one (0..5).
+  // forces one (0..5; any other value: the one-wave tile).  TTS_CODEC_X3P_ILV=0 / 1 forces a
+  // schedule (A/B); TTS_CODEC_X3P_PP=1: PP on the 8-wave tile where the one-stage-ahead schedule
+  // runs; TTS_CODEC_X3P_SMALL4=1: four stages on the one-wave tile (experiments)
   static const int forced = env_int("TTS_CODEC_X3P_TILE", -1);
+  static const int ilv_env = env_int("TTS_CODEC_X3P_ILV", -1);
+  static const bool pp_env = env_set("TTS_CODEC_X3P_PP");
+  static const bool small4 = env_set("TTS_CODEC_X3P_SMALL4");
   auto tiles = [&](int tm, int tn) { return ((g.M + tm - 1) / tm) * ((g.N + tn - 1) / tn); };
   int c = forced;
   if (c < 0)
     c = tiles(256, 128) >= 512 ? 0 : tiles(128, 128) >= 256 ? 1 : tiles(128, 64) >= 256 ? 2 : tiles(64, 64) >= 256 ? 3 : 4;
-  switch (c) {
-    case 0: launch_x3p<256, 128, 4, 2>(g, s); break;
-    case 1: launch_x3p<128, 128, 2, 2>(g, s); break;
-    case 2: launch_x3p<128, 64, 2, 2>(g, s); break;
-    case 3: launch_x3p<64, 64, 2, 2>(g, s); break;
-    case 5: launch_x3p<128, 128, 2, 4, 3>(g, s); break;  // (8 waves of 64x32, three stages: experiment)
-    default:  // one wave: a lone utterance's small GEMMs (TTS_CODEC_X3P_SMALL4=1: four stages, the DMA
-      // three steps ahead — experiment)
-      if (small4()) launch_x3p<32, 32, 1, 1, 4>(g, s);
-      else launch_x3p<32, 32, 1, 1>(g, s);
-      break;
-  }
+  if (c > 5) c = 4;
+  const bool four = c == 4 && small4;
+  const int ilv = (c == 5 || four) ? -1 : ilv_env < 0 ? -1 : ilv_env != 0;
+  launch_gemm_x3p_form(g, c, ilv, pp_env && c == 0 && ilv != 0, four, s);
 }
 
 void x3p_stamps_dump(FILE* f) {

@@ -41,10 +41,27 @@ struct GemmF32Args {
   size_t part_elems = 0;  // capacity of `part`
   int ksplit = 1, kchunk = 0;
 };
+// chooses the form by the problem's size and TTS_CODEC_BX3 / TTS_CODEC_TILE (what the engine calls)
 void launch_gemm_f32(const GemmF32Args& g, hipStream_t s);
-// the same contraction with A and B both given as planes (Ap, Bp; codec_gemm.hip)
+// One instantiation by name (the op-level tests reach every form from one process): the
+// bf16-split kernel gemm_bx3_kernel by tile, _B = B read from its planes (Bp), _AB = A as well
+// (Ap), else split from fp32 while staging; the fp32 MFMA kernel gemm_f32_kernel by tile, with
+// its big K step (64 on 64x64, 32 on 128x128) or _K16.  Throws, launching nothing, where the
+// form cannot run the arguments (an operand it reads missing, K no multiple of its step).
+enum GemmForm {
+  kBx3_256x128_AB = 0, kBx3_128x128_AB, kBx3_256x128_B, kBx3_128x256_B, kBx3_128x128_B, kBx3_64x64_B,
+  kBx3_128x128, kBx3_64x64,
+  kF32_64x64, kF32_64x64_K16, kF32_128x128, kF32_128x128_K16,
+  kGemmForms
+};
+void launch_gemm_f32_form(const GemmF32Args& g, int form, hipStream_t s);
+// the same contraction with A and B both given as planes (Ap, Bp; codec_gemm.hip): the tile by
+// the problem's size and the TTS_CODEC_X3P_* switches (what the engine calls) ...
 bool gemm_x3p_supported(const GemmF32Args& g);
 void launch_gemm_x3p(const GemmF32Args& g, hipStream_t s);
+// ... or one form by name: tile 0..5, ilv 0 / 1 / -1 (the tile's own schedule), pp, four stages;
+// throws, launching nothing, on a combination that does not exist
+void launch_gemm_x3p_form(const GemmF32Args& g, int tile, int ilv, bool pp, bool four, hipStream_t s);
 // diagnostic (stamps) build: print and reset the K-loop phase sums of gemm_x3p; no-op otherwise
 void x3p_stamps_dump(FILE* f);
 // planes[0..3n) = the (h, m, l) bf16 split of x[0..n) the GEMM applies to its operands

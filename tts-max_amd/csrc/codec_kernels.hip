@@ -169,14 +169,18 @@ __global__ void gemm_f32_reduce_kernel(const float* __restrict__ part, int S, in
 // K step per barrier pair: 64 (64x64 tiles) / 32 (128x128) where K allows — enough MFMA
 // work per step to cover the next step's L2 latency; 16 otherwise
 template <int TM, int TN>
-static void launch_tile(const GemmF32Args& g, dim3 grid, hipStream_t s) {
+static bool big_step(const GemmF32Args& g) {
   constexpr int BIG = TM == 128 ? 32 : 64;
-  if (g.kchunk % BIG == 0 && g.K % BIG == 0)
-    hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, BIG>), grid, dim3(256), 0, s, g);
-  else
-    hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, 16>), grid, dim3(256), 0, s, g);
+  return g.kchunk % BIG == 0 && g.K % BIG == 0;
+}
+template <int TM, int TN>
+static void launch_tile(const GemmF32Args& g, dim3 grid, bool big, hipStream_t s) {
+  constexpr int BIG = TM == 128 ? 32 : 64;
+  if (big) hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, BIG>), grid, dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, 16>), grid, dim3(256), 0, s, g);
 }
 
+// Split-K launch (kept with the kernels' `part` path; launch_gemm_f32 never splits, see below).
 // Tiles: 128x128 (4 waves x 2x2 MFMA accumulators, K step 32) when that grid fills the
 // chip, else 64x64 split over K up to ~768 workgroups (measured best at T = 650: 128x128
 // tiles split to the same count were 25 % slower).
@@ -191,14 +195,14 @@ static void launch_split(GemmF32Args g, int target, hipStream_t s) {
   }
   if (S <= 1) {
     g.ksplit = 1; g.kchunk = g.K;
-    launch_tile<TM, TN>(g, dim3(grid), s);
+    launch_tile<TM, TN>(g, dim3(grid), big_step<TM, TN>(g), s);
     return;
   }
   const int step = (g.K % 64 == 0) ? 64 : 16;
   g.kchunk = ((g.K + S - 1) / S + step - 1) / step * step;
   S = (g.K + g.kchunk - 1) / g.kchunk;
   g.ksplit = S;
-  launch_tile<TM, TN>(g, dim3(grid, S), s);
+  launch_tile<TM, TN>(g, dim3(grid, S), big_step<TM, TN>(g), s);
   const long long n = (long long)g.M * g.N;
   hipLaunchKernelGGL(gemm_f32_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g.part, S,
                      g.M, g.N, g.bias, g.act, g.resid, g.C, g.ldc);
@@ -411,20 +415,51 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bx3_kernel(GemmF32Args g) {
   }
 }
 
-// The codec never splits K over workgroups: every output element is one in-order sweep of K
-// whatever the tile shape, so a row's bits do not depend on how many rows share the launch
-// (an utterance decodes to the same samples alone or in any batch).  A ragged batch gives
-// the GEMMs their rows; a lone short utterance leaves CUs idle instead.
-void launch_gemm_f32(const GemmF32Args& g_in, hipStream_t s) {
+// One named instantiation (GemmForm, codec_kernels.h), all of K in one workgroup.  A form that
+// cannot run the arguments throws and launches nothing.
+void launch_gemm_f32_form(const GemmF32Args& g_in, int form, hipStream_t s) {
   GemmF32Args g = g_in;
   g.part = nullptr;
   g.ksplit = 1;
   g.kchunk = g.K;
+  if (g.M < 1 || g.N < 1 || g.K < 1 || (!g.C && !g.Cp)) throw std::runtime_error("codec gemm: empty problem or no output");
+  auto grid = [&](int tm, int tn) { return dim3(((g.M + tm - 1) / tm) * ((g.N + tn - 1) / tn)); };
+  if (form >= kBx3_256x128_AB && form <= kBx3_64x64) {
+    const bool apre = form <= kBx3_128x128_AB, bpre = form <= kBx3_64x64_B;
+    if (g.K % 32 != 0) throw std::runtime_error("codec gemm: the bf16-split forms take K in 32-element steps");
+    if (apre ? !g.Ap : !g.A) throw std::runtime_error(apre ? "codec gemm: the form reads A's planes (Ap)" : "codec gemm: the form reads fp32 A");
+    if (bpre ? !g.Bp : !g.B) throw std::runtime_error(bpre ? "codec gemm: the form reads B's planes (Bp)" : "codec gemm: the form reads fp32 B");
+    switch (form) {
+      case kBx3_256x128_AB: hipLaunchKernelGGL((gemm_bx3_kernel<256, 128, 4, 2, true, true>), grid(256, 128), dim3(512), 0, s, g); break;
+      case kBx3_128x128_AB: hipLaunchKernelGGL((gemm_bx3_kernel<128, 128, 2, 2, true, true>), grid(128, 128), dim3(256), 0, s, g); break;
+      case kBx3_256x128_B: hipLaunchKernelGGL((gemm_bx3_kernel<256, 128, 4, 2, true>), grid(256, 128), dim3(512), 0, s, g); break;
+      case kBx3_128x256_B: hipLaunchKernelGGL((gemm_bx3_kernel<128, 256, 2, 4, true>), grid(128, 256), dim3(512), 0, s, g); break;
+      case kBx3_128x128_B: hipLaunchKernelGGL((gemm_bx3_kernel<128, 128, 2, 2, true>), grid(128, 128), dim3(256), 0, s, g); break;
+      case kBx3_64x64_B: hipLaunchKernelGGL((gemm_bx3_kernel<64, 64, 2, 2, true>), grid(64, 64), dim3(256), 0, s, g); break;
+      case kBx3_128x128: hipLaunchKernelGGL((gemm_bx3_kernel<128, 128, 2, 2, false>), grid(128, 128), dim3(256), 0, s, g); break;
+      default: hipLaunchKernelGGL((gemm_bx3_kernel<64, 64, 2, 2, false>), grid(64, 64), dim3(256), 0, s, g); break;
+    }
+    return;
+  }
+  if (form < kF32_64x64 || form > kF32_128x128_K16) throw std::runtime_error("codec gemm: unknown form");
+  if (!g.A || !g.B) throw std::runtime_error("codec gemm: the fp32 MFMA forms read fp32 A and B");
+  const bool big = form == kF32_64x64 || form == kF32_128x128;
+  const int step = !big ? 16 : form == kF32_64x64 ? 64 : 32;
+  if (g.K % step != 0) throw std::runtime_error("codec gemm: K is not a multiple of the form's K step");
+  if (form <= kF32_64x64_K16) launch_tile<64, 64>(g, grid(64, 64), big, s);
+  else launch_tile<128, 128>(g, grid(128, 128), big, s);
+}
+
+// The codec never splits K over workgroups: every output element is one in-order sweep of K
+// whatever the tile shape, so a row's bits do not depend on how many rows share the launch
+// (an utterance decodes to the same samples alone or in any batch).  A ragged batch gives
+// the GEMMs their rows; a lone short utterance leaves CUs idle instead.
+void launch_gemm_f32(const GemmF32Args& g, hipStream_t s) {
   // TTS_CODEC_BX3=0: plain fp32 MFMA for every contraction
   static const bool bx3 = env_on("TTS_CODEC_BX3");
   const int big = ((g.M + 127) / 128) * ((g.N + 127) / 128);
+  int form;
   if (bx3 && g.K % 32 == 0 && g.lda % 4 == 0) {
-    const dim3 g128(big), g64(((g.M + 63) / 64) * ((g.N + 63) / 64));
     // TTS_CODEC_TILE: 0 = 128x128; 1 (default) = 256x128, 2 = 128x256 (8 waves of 64x64, one
     // workgroup per CU: fewer operand bytes per MAC, and with 256 columns each A element is
     // split for twice the outputs) where those tiles still make >= 2 rounds of the CUs (the
@@ -432,22 +467,20 @@ void launch_gemm_f32(const GemmF32Args& g_in, hipStream_t s) {
     static const int big_tiles = env_int("TTS_CODEC_TILE", 1);
     const int t21 = ((g.M + 255) / 256) * ((g.N + 127) / 128);
     const int t12 = ((g.M + 127) / 128) * ((g.N + 255) / 256);
-    if (g.Bp && g.Ap && big_tiles == 1 && t21 >= 2 * 256)
-      hipLaunchKernelGGL((gemm_bx3_kernel<256, 128, 4, 2, true, true>), dim3(t21), dim3(512), 0, s, g);
-    else if (g.Bp && g.Ap && big >= 256)
-      hipLaunchKernelGGL((gemm_bx3_kernel<128, 128, 2, 2, true, true>), g128, dim3(256), 0, s, g);
-    else if (g.Bp && big_tiles == 1 && t21 >= 2 * 256)
-      hipLaunchKernelGGL((gemm_bx3_kernel<256, 128, 4, 2, true>), dim3(t21), dim3(512), 0, s, g);
-    else if (g.Bp && big_tiles == 2 && t12 >= 2 * 256)
-      hipLaunchKernelGGL((gemm_bx3_kernel<128, 256, 2, 4, true>), dim3(t12), dim3(512), 0, s, g);
-    else if (g.Bp && big >= 256) hipLaunchKernelGGL((gemm_bx3_kernel<128, 128, 2, 2, true>), g128, dim3(256), 0, s, g);
-    else if (g.Bp) hipLaunchKernelGGL((gemm_bx3_kernel<64, 64, 2, 2, true>), g64, dim3(256), 0, s, g);
-    else if (big >= 256) hipLaunchKernelGGL((gemm_bx3_kernel<128, 128, 2, 2, false>), g128, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((gemm_bx3_kernel<64, 64, 2, 2, false>), g64, dim3(256), 0, s, g);
-    return;
+    if (g.Bp && g.Ap && big_tiles == 1 && t21 >= 2 * 256) form = kBx3_256x128_AB;
+    else if (g.Bp && g.Ap && big >= 256) form = kBx3_128x128_AB;
+    else if (g.Bp && big_tiles == 1 && t21 >= 2 * 256) form = kBx3_256x128_B;
+    else if (g.Bp && big_tiles == 2 && t12 >= 2 * 256) form = kBx3_128x256_B;
+    else if (g.Bp && big >= 256) form = kBx3_128x128_B;
+    else if (g.Bp) form = kBx3_64x64_B;
+    else if (big >= 256) form = kBx3_128x128;
+    else form = kBx3_64x64;
+  } else if (big >= 256) {
+    form = g.K % 32 == 0 ? kF32_128x128 : kF32_128x128_K16;
+  } else {
+    form = g.K % 64 == 0 ? kF32_64x64 : kF32_64x64_K16;
   }
-  if (big >= 256) launch_split<128, 128>(g, 0, s);
-  else launch_split<64, 64>(g, 0, s);
+  launch_gemm_f32_form(g, form, s);
 }
 
 // B operand split once (weights at load): planes [3][n] = h, m, l with the kernel's rounding

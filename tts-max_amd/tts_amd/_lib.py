@@ -74,6 +74,8 @@ EXPORTED_SYMBOLS = (
     "tts_op_attn_prefill",
     "tts_op_attn_decode",
     "tts_op_head_pick",
+    "tts_op_split_planes",
+    "tts_op_gemm_planes",
 )
 
 
@@ -207,6 +209,8 @@ def load_library() -> ctypes.CDLL:
         "tts_op_sample_rows": (I32, [P, P, P, I32, I32, I32, P, P, P, P, P, I32, P, P, I32, P, P, P]),
         "tts_op_rmsnorm": (I32, [P, P, F32, P, I32, I32, P]),
         "tts_op_gemm_f32": (I32, [P, I32, I32, I32, P, I32, P, P, I32, P, I32, P]),
+        "tts_op_split_planes": (I32, [P, P, I64, P]),
+        "tts_op_gemm_planes": (I32, [P, P, I64, I32, I32, I32, P, P, I32, P, P, P, I64, I32, P, I32, I32, P]),
         "tts_op_attn_prefill": (I32, [P, I32, pi32, pi32, pi32, I32, I32, P, P, I32, P, P, I32, I32, I32, F32, P, P, P]),
         "tts_op_attn_decode": (I32, [P, P, I32, I32, I32, P, P, I32, P, P, I32, P, P, I32, I32, I32, F32, P, P]),
         "tts_debug_step_plan": (I32, [ctypes.POINTER(LmConfig), I32, I32, ctypes.c_char_p, I32]),
